@@ -24,6 +24,13 @@ One step (per rank, weak scaling -- fixed work per GPU):
 The synthetic filterbank (uniform 2-bit noise, random seed) is generated on
 rank 0's GPU and RCCL-broadcast to the others outside the timed region.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line; nothing else is measured.  ``--dump-outputs DIR`` also writes the last
+timed step's result (rank 0's merged, scored candidates) as ``DIR/*.npy``:
+the inputs depend on the arguments alone, so two builds can be compared
+output for output.  ``--full`` is where any measurement beyond the headline
+figure belongs (none exists at present).
+
 Prints ONE JSON line on rank 0.  Reference number: BASELINE.md has no
 published 2^23 figure; the N*log N extrapolation of the golden-run search
 throughput (573 trials/s at 2^17 on 2x Tesla C2070) is ~6.6 trials/s, used
@@ -80,7 +87,48 @@ def parse():
                         "shard [r*dms, (r+1)*dms)), one JSON line per r: checks that every rank's step costs the same")
     p.add_argument("--rfi-amp", type=float, default=0.05,
                    help="--signal: amplitude of the two undispersed RFI pulse trains (the pulsars: 0.05-0.08)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps, write what the last timed step returned (rank 0's merged, scored "
+                        "candidate list) as DIR/candidates.npy and DIR/candidate_members.npy (float64)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline figure (none at present: each figure "
+                        "of the result line comes out of the timed steps themselves)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20  # all of --dump-outputs together
+CANDIDATE_COLUMNS = ("dm", "dm_idx", "acc", "nh", "snr", "freq", "is_adjacent", "is_physical",
+                     "ddm_count_ratio", "ddm_snr_ratio", "nassoc")
+MEMBER_COLUMNS = ("candidate", "dm", "dm_idx", "acc", "nh", "snr", "freq")
+
+
+def dump_outputs(outdir, cands, seed) -> dict:
+    """Write a step's result -- the merged, scored candidate list the caller
+    of the timed path receives -- as float64 arrays in the list's own order:
+    candidates.npy, one row per candidate (CANDIDATE_COLUMNS), and
+    candidate_members.npy, one row per detection a candidate holds (itself
+    first, then its association tree depth first: MEMBER_COLUMNS, `candidate`
+    the row of candidates.npy).  Above DUMP_MAX_BYTES in all, a seeded sample
+    of the rows (the same rows for the same seed and row counts), in order."""
+    import numpy as np
+
+    top = np.array([[getattr(c, k) for k in CANDIDATE_COLUMNS[:-1]] + [c.count_assoc()] for c in cands],
+                   dtype=np.float64).reshape(-1, len(CANDIDATE_COLUMNS))
+    mem = np.array([(i,) + tuple(pod) for i, c in enumerate(cands) for pod in c.pods()],
+                   dtype=np.float64).reshape(-1, len(MEMBER_COLUMNS))
+    rows = {"candidates": len(top), "candidate_members": len(mem)}
+    rng = np.random.default_rng(seed)
+    budget = DUMP_MAX_BYTES // 2 - 4096  # per array, the .npy header included
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in (("candidates", top), ("candidate_members", mem)):
+        keep = budget // (8 * arr.shape[1])
+        if len(arr) > keep:
+            arr = arr[np.sort(rng.choice(len(arr), size=keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+    return rows
 
 
 def main() -> int:
@@ -246,7 +294,8 @@ def main() -> int:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     pending = run_steps(a.steps)
-    ncands = len(finish(pending[-1]))
+    last = finish(pending[-1])
+    ncands = len(last)
     for r in pending:
         finish(r)
     torch.cuda.synchronize()
@@ -257,6 +306,7 @@ def main() -> int:
     value = trials_per_step * a.steps / elapsed
     ctr = rs.counters()  # timed steps only: peaks compacted on the GPU, host clustering + distillation time
     if ctx.is_root:
+        dumped = dump_outputs(a.dump_outputs, last, a.seed) if a.dump_outputs else None
         out = {
             "metric": "DM×accel trials/sec, 2^23-sample series, 8-harmonic sum",
             "value": round(value, 2),
@@ -310,6 +360,9 @@ def main() -> int:
                 "tail_s_per_step": round(ctr.get("tail_s", 0) / a.steps, 4),
                 "trials_distilled_on_gpu": int(ctr.get("gpu_distilled", 0)),
                 "trials_distilled_on_host": int(ctr.get("host_distilled", 0)),
+                "full": bool(a.full),
+                # --dump-outputs: rows of the last step's result before any sampling
+                "outputs_dumped": dumped,
             },
         }
         print(json.dumps(out), flush=True)
