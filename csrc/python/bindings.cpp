@@ -119,6 +119,7 @@ SigprocHeader dict_to_header(const py::dict& d) {
 }  // namespace
 
 void bind_ffa(py::module_& m);  // bind_ffa.cpp
+void bind_sp(py::module_& m);   // bind_sp.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -689,6 +690,7 @@ PYBIND11_MODULE(_C, m) {
 
   // ------------------------------------------------------------- kernels --
   bind_ffa(m);
+  bind_sp(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -1,4 +1,5 @@
 #include "psoup/cli.hpp"
+#include "psoup/singlepulse.hpp"
 
 #include <cstdlib>
 #include <ctime>
@@ -331,6 +332,35 @@ bool parse_ffa_cmdline(FfaCmdLineOptions& a, const std::vector<std::string>& arg
       val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
   };
   return run_parser(specs, argv, "Peasoup/FFAster extension - a GPU FFA pulsar search pipeline", nullptr, exit_now);
+}
+
+std::string default_sp_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_spsearch.output", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_sp_cmdline(SpCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_sp_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_n("t", "num_threads", "The number of GPUs to use", a.max_num_threads),
+      val_n("", "dm_start", "First DM to dedisperse to", a.dm_start),
+      val_n("", "dm_end", "Last DM to dedisperse to", a.dm_end),
+      val_n("", "dm_tol", "DM smearing tolerance (1.11=10%)", a.dm_tol),
+      val_n("", "dm_pulse_width", "Minimum pulse width for which dm_tol is valid", a.dm_pulse_width),
+      sw("v", "verbose", "verbose mode", a.verbose),
+      sw("p", "progress_bar", "Enable progress bar for DM search", a.progress_bar),
+      val_n("m", "min_snr", "Minimum boxcar S/N of a single pulse", a.min_snr),
+      val_n("", "boxcar_max", "Widest boxcar in samples (widths are the powers of two up to it)", a.boxcar_max),
+      val_n("", "baseline", "Length of the trend blocks in seconds", a.baseline),
+      val_n("", "limit", "Upper limit on the number of candidates written", a.limit),
+      val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
+  };
+  return run_parser(specs, argv, "Peasoup single-pulse extension - a GPU transient search pipeline", nullptr, exit_now);
 }
 
 }  // namespace psoup

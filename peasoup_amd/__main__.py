@@ -1,5 +1,6 @@
 """``python -m peasoup_amd [peasoup flags]`` (or ``python -m peasoup_amd ffa
-[ffaster flags]`` for the FFA search) -- the peasoup CLI as a
+[ffaster flags]`` for the FFA search, ``python -m peasoup_amd sps [spsearch
+flags]`` for the single-pulse search) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -63,6 +64,8 @@ def main(argv=None) -> int:
     argv = list(sys.argv if argv is None else argv)
     if len(argv) > 1 and argv[1] == "ffa":
         return _main_ffa(["ffaster"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "sps":
+        return _main_sps(["spsearch"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -100,6 +103,27 @@ def _main_ffa(argv) -> int:
         _fail_hard("ffa", e)
     if res is not None and args.verbose:
         print(f"Wrote {len(res.candidates)} FFA candidates to {args.outfilename}")
+    pdist.shutdown()
+    return 0
+
+
+def _main_sps(argv) -> int:
+    from . import _C
+    from .models.singlepulse import run_single_pulse_search
+    from .parallel import dist as pdist
+
+    ok, exit_now, args = _C.parse_sp_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = run_single_pulse_search(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("sps", e)
+    if res is not None and args.verbose:
+        print(f"Wrote {len(res.candidates)} single-pulse candidates to {args.outfilename}")
     pdist.shutdown()
     return 0
 

@@ -36,5 +36,6 @@ from .core import (  # noqa: F401
     resample_v1,
     rfft,
     running_median,
+    single_pulse_search,
     unpack_transpose,
 )

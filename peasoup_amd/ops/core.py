@@ -459,3 +459,26 @@ def cmul_(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """y <- x * y (complex, in place)."""
     K.cmul_inplace(_cplx_ptr(x), _cplx_ptr(y), y.numel(), _s())
     return y
+
+
+# ----------------------------------------------------------- single pulses --
+def single_pulse_search(trials: torch.Tensor, nsamps: int, params, dm_idx0: int = 0, dense: bool = False):
+    """Boxcar single-pulse search of uint8 trials [ndm, row_stride] (the first
+    ``nsamps`` samples of each row; row_stride a multiple of 4) with a
+    ``_C.SpParams``.  Returns the ``_C.SpEvent`` list sorted by (dm_idx,
+    width_log2, sample); with ``dense`` also the per-block maximum S/N
+    (float32) and its sample (int64, -1 where a block has no valid start),
+    each [ndm, K + 1, ceil(nsamps / 64)]."""
+    _check(trials, torch.uint8, "trials")
+    if trials.dim() != 2:
+        raise ValueError("trials must be [ndm, row_stride]")
+    ndm, stride = int(trials.shape[0]), int(trials.shape[1])
+    eng = _C.SinglePulseEngine(params, int(nsamps), _s())
+    if not dense:
+        return eng.search_block(trials.data_ptr(), stride, ndm, int(dm_idx0))
+    shape = (ndm, len(eng.widths), (int(nsamps) + _C.SP_BLOCK - 1) // _C.SP_BLOCK)
+    snr = torch.empty(shape, dtype=torch.float32, device=trials.device)
+    arg = torch.empty(shape, dtype=torch.int32, device=trials.device)  # the kernel's uint32, 0xffffffff = -1
+    ev = eng.search_block(trials.data_ptr(), stride, ndm, int(dm_idx0), snr.data_ptr(), arg.data_ptr())
+    arg = arg.to(torch.int64) & 0xFFFFFFFF
+    return ev, snr, torch.where(arg == 0xFFFFFFFF, torch.full_like(arg, -1), arg)

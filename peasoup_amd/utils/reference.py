@@ -376,3 +376,89 @@ def ffa_downsample(x: np.ndarray, f: float) -> np.ndarray:
     j = np.arange(nout + 1, dtype=np.float64) * f
     I = integ(j)
     return I[1:] - I[:-1]
+
+
+# ------------------------------------------------------- single pulses ------
+# Float64 oracle of the single-pulse search, written from its definition
+# (csrc/include/psoup/singlepulse.hpp), not from the kernel.
+def sp_widths(n: int, wmax: int) -> List[int]:
+    """Powers of two up to min(wmax, n // 2)."""
+    out, w = [], 1
+    while w <= min(int(wmax), int(n) // 2):
+        out.append(w)
+        w *= 2
+    return out
+
+
+def sp_trend(u8: np.ndarray, baseline: int) -> np.ndarray:
+    """Block means over `baseline` samples (exact integer sums), linear
+    between block centres, flat before the first and after the last."""
+    u = np.asarray(u8)
+    n = len(u)
+    nblk = (n + baseline - 1) // baseline
+    means = np.array([u[b * baseline:(b + 1) * baseline].astype(np.int64).sum() /
+                      float(len(u[b * baseline:(b + 1) * baseline])) for b in range(nblk)], dtype=np.float64)
+    if nblk == 1:
+        return np.full(n, means[0])
+    pos = (np.arange(n, dtype=np.float64) - 0.5 * baseline) / baseline  # in block-centre units
+    return np.interp(pos, np.arange(nblk, dtype=np.float64), means)  # clamps outside [0, nblk - 1]
+
+
+def sp_boxcar_snr(u8: np.ndarray, baseline: int, widths) -> List[np.ndarray]:
+    """snr_k[i] = sum(x[i:i + w_k]) / (sigma sqrt(w_k)) for 0 <= i <= n - w_k,
+    x = u8 - trend, sigma = sqrt(mean(x^2)); all zeros when sigma == 0."""
+    x = np.asarray(u8, dtype=np.float64) - sp_trend(u8, baseline)
+    n = len(x)
+    sigma = math.sqrt(float(np.mean(x * x)))
+    c = np.concatenate([[0.0], np.cumsum(x)])
+    out = []
+    for w in widths:
+        s = c[w:n + 1] - c[:n + 1 - w]
+        out.append(s / (sigma * math.sqrt(w)) if sigma > 0 else np.zeros_like(s))
+    return out
+
+
+def sp_block_maxima(snr: Sequence[np.ndarray], block: int = 64):
+    """Per width: (maxima, argmax) over the aligned blocks of `block` start
+    samples that hold at least one start (the last may be partial); the
+    lowest index on a tie."""
+    out = []
+    for s in snr:
+        nb = (len(s) + block - 1) // block
+        mx = np.empty(nb, dtype=np.float64)
+        am = np.empty(nb, dtype=np.int64)
+        for b in range(nb):
+            seg = s[b * block:(b + 1) * block]
+            j = int(np.argmax(seg))  # first occurrence
+            mx[b], am[b] = seg[j], b * block + j
+        out.append((mx, am))
+    return out
+
+
+def sp_cluster_ref(events, dm_list, band_delay_per_dm: float, tsamp: float) -> List[Dict]:
+    """Literal transcription of the clustering rule.  events: (sample,
+    width_log2, snr, dm_idx) tuples.  Taken in descending S/N (ties: dm_idx,
+    width_log2, sample); with t = sample + w / 2 an event joins the first
+    accepted candidate with |t - t0| <= (w + w0) / 2 + |dm - dm0| *
+    band_delay_per_dm / tsamp, else it founds a candidate."""
+    order = sorted(events, key=lambda e: (-float(e[2]), int(e[3]), int(e[1]), int(e[0])))
+    cands: List[Dict] = []
+    for sample, k, snr, d in order:
+        sample, k, d = int(sample), int(k), int(d)
+        w = 1 << k
+        dm = float(dm_list[d])
+        t = sample + 0.5 * w
+        for c in cands:
+            slack = abs(dm - c["dm"]) * band_delay_per_dm / tsamp
+            if abs(t - c["t"]) <= 0.5 * (w + c["width"]) + slack:
+                c["members"] += 1
+                c["first_sample"] = min(c["first_sample"], sample)
+                c["last_sample"] = max(c["last_sample"], sample + w - 1)
+                c["dm_idx_lo"] = min(c["dm_idx_lo"], d)
+                c["dm_idx_hi"] = max(c["dm_idx_hi"], d)
+                break
+        else:
+            cands.append({"sample": sample, "t": t, "time_s": t * tsamp, "width": w, "snr": float(snr), "dm": dm,
+                          "dm_idx": d, "members": 1, "first_sample": sample, "last_sample": sample + w - 1,
+                          "dm_idx_lo": d, "dm_idx_hi": d})
+    return cands

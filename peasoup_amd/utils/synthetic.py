@@ -28,14 +28,25 @@ class PulsarSpec:
     phase: float = 0.0
 
 
+@dataclass
+class BurstSpec:
+    """One dispersed Gaussian pulse (a single-pulse search target)."""
+    time: float = 1.0           # arrival time in the top channel (s)
+    dm: float = 30.0            # pc cm^-3
+    width: float = 5e-3         # FWHM (s)
+    amplitude: float = 1.0      # peak in units of the per-channel noise sigma
+
+
 def make_header(nchans: int = 64, nbits: int = 2, tsamp: float = 320e-6, fch1: float = 1510.0,
                 foff: float = -1.09, nsamples: int = 0, source_name: str = "synthetic") -> Dict:
     return {"source_name": source_name, "tsamp": tsamp, "fch1": fch1, "foff": foff, "nchans": nchans,
             "nbits": nbits, "nifs": 1, "data_type": 1, "tstart": 50000.0, "nsamples": nsamples}
 
 
-def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 1 << 16) -> np.ndarray:
-    """Return [nsamps, nchans] uint8 quantised samples (values < 2^nbits)."""
+def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 1 << 16, bursts=()) -> np.ndarray:
+    """Return [nsamps, nchans] uint8 quantised samples (values < 2^nbits).
+    ``bursts``: :class:`BurstSpec` pulses, dispersed like the pulsars (they
+    draw nothing from the generator: the noise is the same with or without)."""
     rng = np.random.default_rng(seed)
     nchans = int(header["nchans"])
     nbits = int(header["nbits"])
@@ -62,21 +73,26 @@ def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 
             d = np.minimum(ph, 1.0 - ph)
             w = p.duty / 2.3548
             x += p.amplitude * np.exp(-0.5 * (d / w) ** 2).astype(np.float32)
+        for b in bursts:
+            delay = 4.15e3 * b.dm * (1.0 / freqs ** 2 - 1.0 / fch1 ** 2)  # seconds
+            d = t - delay[None, :] - b.time
+            w = b.width / 2.3548
+            x += b.amplitude * np.exp(-0.5 * (d / w) ** 2).astype(np.float32)
         q = np.rint(mean + sigma * x)
         out[t0:t1] = np.clip(q, 0, levels).astype(np.uint8)
     return out
 
 
-def write(path: str, nsamps: int, header: Optional[Dict] = None, pulsars=(), seed: int = 0) -> Dict:
+def write(path: str, nsamps: int, header: Optional[Dict] = None, pulsars=(), seed: int = 0, bursts=()) -> Dict:
     hdr = dict(header or make_header())
     hdr["nsamples"] = nsamps
-    vals = generate(nsamps, hdr, pulsars, seed)
+    vals = generate(nsamps, hdr, pulsars, seed, bursts=bursts)
     write_filterbank(path, hdr, vals)
     return hdr
 
 
-def packed(nsamps: int, header: Dict, pulsars=(), seed: int = 0) -> np.ndarray:
-    return pack_samples(generate(nsamps, header, pulsars, seed), int(header["nbits"]))
+def packed(nsamps: int, header: Dict, pulsars=(), seed: int = 0, bursts=()) -> np.ndarray:
+    return pack_samples(generate(nsamps, header, pulsars, seed, bursts=bursts), int(header["nbits"]))
 
 
 def generate_packed_torch(nsamps: int, header: Dict, pulsars=(), seed: int = 0, device=None,
