@@ -120,6 +120,7 @@ SigprocHeader dict_to_header(const py::dict& d) {
 
 void bind_ffa(py::module_& m);  // bind_ffa.cpp
 void bind_sp(py::module_& m);   // bind_sp.cpp
+void bind_cube(py::module_& m);  // bind_cube.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -691,6 +692,7 @@ PYBIND11_MODULE(_C, m) {
   // ------------------------------------------------------------- kernels --
   bind_ffa(m);
   bind_sp(m);
+  bind_cube(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -1,4 +1,5 @@
 #include "psoup/cli.hpp"
+#include "psoup/foldcube.hpp"
 #include "psoup/singlepulse.hpp"
 
 #include <cstdlib>
@@ -361,6 +362,64 @@ bool parse_sp_cmdline(SpCmdLineOptions& a, const std::vector<std::string>& argv,
       val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
   };
   return run_parser(specs, argv, "Peasoup single-pulse extension - a GPU transient search pipeline", nullptr, exit_now);
+}
+
+std::string default_cube_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_foldcube.cubes", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_cube_cmdline(FoldCubeCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_cube_output_filename();
+  long long fold_nsamps = static_cast<long long>(a.fold_nsamps);
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_s("", "candfile", "Candidate list: one 'period_s dm acc' per line, '#' comments", a.candfilename),
+      val_s("", "overview", "overview.xml of a finished search (python -m peasoup_amd cube only)",
+            a.overviewfilename),
+      val_n("", "top", "Candidates taken from the top of --overview", a.top),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_n("", "nints", "Subintegrations per cube (1..256)", a.nints),
+      val_n("", "nsub", "Subbands per cube (1..nchans; capped at nchans)", a.nsub),
+      val_n("", "nbins", "Phase bins per cube (2..256)", a.nbins),
+      val_n("", "fold_nsamps", "Samples folded (0 = the largest power of two that fits every candidate)",
+            fold_nsamps),
+      val_n("", "limit", "At most this many candidates from the top of the list", a.limit),
+      sw("v", "verbose", "verbose mode", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup fold-cube extension - subint x subband x phase cubes of candidates", nullptr,
+                  exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.candfilename.empty() == a.overviewfilename.empty()) {
+    std::cerr << "Error: give exactly one of --candfile and --overview" << std::endl;
+    return false;
+  }
+  if (a.nints < 1 || a.nints > 256) {
+    std::cerr << "Error: --nints must be in 1..256" << std::endl;
+    return false;
+  }
+  if (a.nbins < 2 || a.nbins > 256) {
+    std::cerr << "Error: --nbins must be in 2..256" << std::endl;
+    return false;
+  }
+  if (a.nsub < 1) {
+    std::cerr << "Error: --nsub must be at least 1" << std::endl;
+    return false;
+  }
+  if (fold_nsamps < 0) {
+    std::cerr << "Error: --fold_nsamps must be non-negative" << std::endl;
+    return false;
+  }
+  a.fold_nsamps = static_cast<uint64_t>(fold_nsamps);
+  if (a.top < 1 || a.limit < 0) {
+    std::cerr << "Error: --top must be at least 1 and --limit non-negative" << std::endl;
+    return false;
+  }
+  return true;
 }
 
 }  // namespace psoup

@@ -1,6 +1,7 @@
 """``python -m peasoup_amd [peasoup flags]`` (or ``python -m peasoup_amd ffa
 [ffaster flags]`` for the FFA search, ``python -m peasoup_amd sps [spsearch
-flags]`` for the single-pulse search) -- the peasoup CLI as a
+flags]`` for the single-pulse search, ``python -m peasoup_amd cube [foldcube
+flags]`` for the filterbank fold cubes of candidates) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -66,6 +67,8 @@ def main(argv=None) -> int:
         return _main_ffa(["ffaster"] + argv[2:])
     if len(argv) > 1 and argv[1] == "sps":
         return _main_sps(["spsearch"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "cube":
+        return _main_cube(["foldcube"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -125,6 +128,25 @@ def _main_sps(argv) -> int:
     if res is not None and args.verbose:
         print(f"Wrote {len(res.candidates)} single-pulse candidates to {args.outfilename}")
     pdist.shutdown()
+    return 0
+
+
+def _main_cube(argv) -> int:
+    from . import _C
+    from .models.foldcube import run_fold_cubes
+
+    ok, exit_now, args = _C.parse_cube_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        run = run_fold_cubes(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("cube", e)
+    if run is not None and args.verbose:
+        print(f"Wrote {run.ncand} fold cubes to {args.outfilename}")
     return 0
 
 

@@ -482,3 +482,37 @@ def single_pulse_search(trials: torch.Tensor, nsamps: int, params, dm_idx0: int 
     ev = eng.search_block(trials.data_ptr(), stride, ndm, int(dm_idx0), snr.data_ptr(), arg.data_ptr())
     arg = arg.to(torch.int64) & 0xFFFFFFFF
     return ev, snr, torch.where(arg == 0xFFFFFFFF, torch.full_like(arg, -1), arg)
+
+
+# -------------------------------------------------------------- fold cubes --
+def fold_cube(chan_major: torch.Tensor, offsets: torch.Tensor, periods, accels, tsamp: float, fold_nsamps: int,
+              nints: int = 16, nsub: int = 32, nbins: int = 64, bias: int = 0, killmask=None,
+              batch_bytes: int = None):
+    """Folds the channel-major int8 filterbank ``chan_major`` [nchans, stride]
+    (raw sample = stored value + ``bias``; stride a multiple of 16) into one
+    subint x subband x phase cube per candidate: ``offsets`` int32 [ncand,
+    nchans] sample offsets, ``periods`` (s) and ``accels`` (m/s^2) of length
+    ncand.  Returns (sums int64 [ncand, nints, nsub, nbins], hits int32
+    [ncand, nints, nbins]); integer sums, exactly the NumPy oracle's
+    (utils.reference.fold_cube).  Every candidate is validated before
+    anything is launched (``NativeError`` naming the candidate)."""
+    _check(chan_major, torch.int8, "chan_major")
+    if chan_major.dim() != 2:
+        raise ValueError("chan_major must be [nchans, stride]")
+    nchans, stride = int(chan_major.shape[0]), int(chan_major.shape[1])
+    off = offsets.detach().to("cpu", torch.int32).contiguous()
+    periods = [float(p) for p in periods]
+    accels = [float(a) for a in accels]
+    ncand = len(periods)
+    if off.dim() != 2 or tuple(off.shape) != (ncand, nchans) or len(accels) != ncand:
+        raise ValueError("offsets must be [ncand, nchans]; periods and accels of length ncand")
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    params = _C.CubeParams(int(nints), int(nsub), int(nbins), int(fold_nsamps))
+    kw = {} if batch_bytes is None else {"batch_bytes": int(batch_bytes)}
+    folder = _C.CubeFolder(chan_major.data_ptr(), stride, stride, nchans, int(bias), float(tsamp), [], kill, params,
+                           _s(), **kw)
+    sums = torch.empty((ncand, int(nints), int(nsub), int(nbins)), dtype=torch.int64, device=chan_major.device)
+    hits = torch.empty((ncand, int(nints), int(nbins)), dtype=torch.int32, device=chan_major.device)
+    if ncand:
+        folder.fold_offsets(off.numpy(), periods, accels, sums.data_ptr(), hits.data_ptr())
+    return sums, hits

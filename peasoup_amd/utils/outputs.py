@@ -171,3 +171,85 @@ class PeasoupOutput:
                          f"{r['nh']:d} {r['snr']:.2f} {r['folded_snr']:.2f} {r['is_adjacent']:d} {r['is_physical']:d} "
                          f"{r['ddm_count_ratio']:.4f} {r['ddm_snr_ratio']:.4f} {r['nassoc']:d}")
         return "\n".join(lines)
+
+
+# ------------------------------------------------------------ fold cubes ----
+CUBE_MAGIC = b"PSCUBE01"
+_CUBE_HEADER = struct.Struct("<8s6IQ3d")  # magic, ncand nints nsub nbins nchans nbits, fold_nsamps, tsamp fch1 foff
+_CUBE_CAND = struct.Struct("<dff")        # period, dm, acc
+CUBE_HEADER_FIELDS = ("ncand", "nints", "nsub", "nbins", "nchans", "nbits", "fold_nsamps", "tsamp", "fch1", "foff")
+
+
+def write_cube_file(path: str, header: Dict, cands: List[Dict]) -> None:
+    """Writes a fold-cube file byte for byte as the native ``write_cube_file``
+    (csrc/src/foldcube.cpp): little-endian header ``PSCUBE01``, uint32 ncand
+    nints nsub nbins nchans nbits, uint64 fold_nsamps, double tsamp fch1 foff;
+    per candidate double period, float dm, float acc, int32 nactive[nsub],
+    int32 hits[nints][nbins], int64 sums[nints][nsub][nbins].  ``header`` needs
+    every field but ncand; each of ``cands`` is a dict(period, dm, acc,
+    nactive, hits, sums).  Written to a temporary file, then renamed."""
+    import os
+
+    ni, ns, nb = int(header["nints"]), int(header["nsub"]), int(header["nbins"])
+    blob = [_CUBE_HEADER.pack(CUBE_MAGIC, len(cands), ni, ns, nb, int(header["nchans"]), int(header["nbits"]),
+                              int(header["fold_nsamps"]), float(header["tsamp"]), float(header["fch1"]),
+                              float(header["foff"]))]
+    for i, c in enumerate(cands):
+        na = np.ascontiguousarray(c["nactive"], dtype="<i4")
+        hits = np.ascontiguousarray(c["hits"], dtype="<i4")
+        sums = np.ascontiguousarray(c["sums"], dtype="<i8")
+        if na.shape != (ns,) or hits.shape != (ni, nb) or sums.shape != (ni, ns, nb):
+            raise ValueError(f"cube file: candidate {i} has the wrong shape")
+        blob += [_CUBE_CAND.pack(float(c["period"]), float(c["dm"]), float(c["acc"])), na.tobytes(), hits.tobytes(),
+                 sums.tobytes()]
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class FoldCubeFile:
+    """Reader of a fold-cube file (``bin/foldcube`` / ``python -m peasoup_amd
+    cube``): ``len``, ``header``, ``candidate(i)``, ``mean(i)``."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._buf = open(path, "rb").read()
+        if len(self._buf) < _CUBE_HEADER.size or self._buf[:8] != CUBE_MAGIC:
+            raise ValueError(f"{path}: not a fold-cube file")
+        vals = _CUBE_HEADER.unpack_from(self._buf, 0)[1:]
+        self.header: Dict = dict(zip(CUBE_HEADER_FIELDS, vals))
+        ni, ns, nb = self.header["nints"], self.header["nsub"], self.header["nbins"]
+        self._rec = _CUBE_CAND.size + 4 * ns + 4 * ni * nb + 8 * ni * ns * nb
+        if len(self._buf) != _CUBE_HEADER.size + self.header["ncand"] * self._rec:
+            raise ValueError(f"{path}: truncated fold-cube file")
+
+    def __len__(self) -> int:
+        return int(self.header["ncand"])
+
+    def candidate(self, i: int) -> Dict:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        ni, ns, nb = self.header["nints"], self.header["nsub"], self.header["nbins"]
+        o = _CUBE_HEADER.size + i * self._rec
+        period, dm, acc = _CUBE_CAND.unpack_from(self._buf, o)
+        o += _CUBE_CAND.size
+        na = np.frombuffer(self._buf, "<i4", ns, o).copy()
+        o += 4 * ns
+        hits = np.frombuffer(self._buf, "<i4", ni * nb, o).reshape(ni, nb).copy()
+        o += 4 * ni * nb
+        sums = np.frombuffer(self._buf, "<i8", ni * ns * nb, o).reshape(ni, ns, nb).copy()
+        return {"period": period, "dm": dm, "acc": acc, "nactive": na, "hits": hits, "sums": sums}
+
+    def mean(self, i: int) -> np.ndarray:
+        """float64 [nints, nsub, nbins]: sums / (hits * nactive), 0 where that product is 0."""
+        return cube_mean(self.candidate(i))
+
+
+def cube_mean(cand: Dict) -> np.ndarray:
+    """Mean cube of a candidate dict: sums / (hits * nactive) in float64, 0 where the product is 0."""
+    den = (np.asarray(cand["hits"], dtype=np.float64)[:, None, :] *
+           np.asarray(cand["nactive"], dtype=np.float64)[None, :, None])
+    out = np.zeros(den.shape, dtype=np.float64)
+    np.divide(np.asarray(cand["sums"], dtype=np.float64), den, out=out, where=den != 0)
+    return out

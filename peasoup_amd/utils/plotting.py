@@ -65,6 +65,34 @@ def candidate_panels(out: PeasoupOutput, idx: int) -> Dict[str, object]:
     return p
 
 
+def freq_phase_panel(cand: Dict) -> np.ndarray:
+    """Frequency-phase panel of a fold-cube candidate (``FoldCubeFile.candidate``):
+    float64 [nsub, nbins], the mean raw sample over all subints (sums over
+    subints / (hits over subints x nactive)), each subband's median over its
+    filled bins removed, killed subbands (and bins without hits) 0."""
+    sums = np.asarray(cand["sums"], dtype=np.float64).sum(axis=0)
+    hits = np.asarray(cand["hits"], dtype=np.float64).sum(axis=0)
+    nact = np.asarray(cand["nactive"], dtype=np.float64)
+    den = nact[:, None] * hits[None, :]
+    out = np.zeros(den.shape, dtype=np.float64)
+    np.divide(sums, den, out=out, where=den != 0)
+    filled = hits > 0
+    for s in range(out.shape[0]):
+        if nact[s] > 0 and filled.any():
+            out[s, filled] -= np.median(out[s, filled])
+    return out
+
+
+def time_phase_panel(cand: Dict) -> np.ndarray:
+    """Time-phase panel of a fold-cube candidate: float64 [nints, nbins], the
+    mean raw sample over the unkilled channels (0 in bins without hits)."""
+    sums = np.asarray(cand["sums"], dtype=np.float64).sum(axis=1)
+    den = np.asarray(cand["hits"], dtype=np.float64) * float(np.asarray(cand["nactive"]).sum())
+    out = np.zeros(den.shape, dtype=np.float64)
+    np.divide(sums, den, out=out, where=den != 0)
+    return out
+
+
 def _sizes(snr: np.ndarray) -> np.ndarray:
     s = np.asarray(snr, dtype=np.float64)
     if s.size == 0:
@@ -79,7 +107,15 @@ class CandidatePlotter:
     ``.npz`` panels when matplotlib is missing) and returns its path."""
 
     def __init__(self, outdir: Optional[str] = None, overview: Optional[str] = None,
-                 candidates: Optional[str] = None):
+                 candidates: Optional[str] = None, cubes: Optional[str] = None):
+        # cubes: a fold-cube file whose candidate i belongs to candidate i of
+        # the overview (python -m peasoup_amd cube --overview); adds the
+        # frequency-phase and time-phase panels
+        self.cubes = None
+        if cubes:
+            from .outputs import FoldCubeFile
+
+            self.cubes = FoldCubeFile(cubes)
         overview = overview or os.path.join(outdir, "overview.xml")
         candidates = candidates or os.path.join(os.path.dirname(os.path.abspath(overview)), "candidates.peasoup")
         self.out = PeasoupOutput(overview, candidates)
@@ -102,6 +138,10 @@ class CandidatePlotter:
 
     def plot_cand(self, idx: int, filename: Optional[str] = None) -> str:
         p = candidate_panels(self.out, idx)
+        if self.cubes is not None and idx < len(self.cubes):
+            cube = self.cubes.candidate(idx)
+            p["freq_phase"] = freq_phase_panel(cube)
+            p["time_phase"] = time_phase_panel(cube)
         if self._plt is None:
             path = (filename or f"cand_{idx:04d}") + ("" if str(filename).endswith(".npz") else ".npz")
             arrays = {k: v for k, v in p.items() if isinstance(v, np.ndarray)}
@@ -110,6 +150,8 @@ class CandidatePlotter:
             return path
         path = filename or f"cand_{idx:04d}.png"
         fig = self._draw(p)
+        if "freq_phase" in p:
+            self._draw_cube(fig, p)
         fig.savefig(path)
         self._plt.close(fig)
         return path
@@ -181,6 +223,22 @@ class CandidatePlotter:
         all_ax.set_ylabel("DM (pc cm^-3)")
         fig.suptitle(f"{p['title']}  candidate {p['index']}")
         return fig
+
+    # the two fold-cube panels, in a strip added to the right of the figure
+    def _draw_cube(self, fig, p: Dict[str, object]) -> None:
+        w, h = fig.get_size_inches()
+        fig.set_size_inches(w + 4.0, h)
+        fig.subplots_adjust(right=w / (w + 4.0) * 0.9)
+        left = w / (w + 4.0) * 0.9 + 0.05
+        fp_ax = fig.add_axes([left, 0.55, 0.98 - left, 0.33])
+        tp_ax = fig.add_axes([left, 0.10, 0.98 - left, 0.33])
+        fp_ax.imshow(p["freq_phase"], aspect="auto", interpolation="nearest", origin="lower")
+        fp_ax.set_title("Frequency-phase (filterbank fold)")
+        fp_ax.set_ylabel("Subband")
+        tp_ax.imshow(p["time_phase"], aspect="auto", interpolation="nearest", origin="lower")
+        tp_ax.set_title("Time-phase (filterbank fold)")
+        tp_ax.set_ylabel("Subintegration")
+        tp_ax.set_xlabel("Phase bin")
 
 
 def plot_all(outdir: str, limit: int = 100, dest: Optional[str] = None) -> List[str]:

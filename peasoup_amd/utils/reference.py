@@ -462,3 +462,34 @@ def sp_cluster_ref(events, dm_list, band_delay_per_dm: float, tsamp: float) -> L
                           "dm_idx": d, "members": 1, "first_sample": sample, "last_sample": sample + w - 1,
                           "dm_idx_lo": d, "dm_idx_hi": d})
     return cands
+
+
+# ------------------------------------------------------------ fold cubes ----
+def fold_cube(values: np.ndarray, offsets: np.ndarray, period: float, af: float, tsamp: float, n: int, nints: int,
+              nsub: int, nbins: int, killmask=None):
+    """Filterbank fold cube of one candidate, written from the definition in
+    csrc/include/psoup/foldcube.hpp.  values [nsamps, nchans] raw samples
+    (>= 0), offsets int [nchans], af from accel_factor.  Returns (sums int64
+    [nints, nsub, nbins], hits int32 [nints, nbins], nactive int32 [nsub])."""
+    nsamps, nchans = values.shape
+    kill = np.ones(nchans, bool) if killmask is None else np.asarray(killmask) != 0
+    off = np.asarray(offsets, dtype=np.int64)
+    if int(off.max()) + n > nsamps or int(off.min()) < 0:
+        raise ValueError("fold_cube: max(off) + n <= nsamps is required")
+    nps = n // nints
+    h = n / 2.0
+    d = np.arange(nints * nps, dtype=np.float64)
+    subint = np.arange(nints * nps, dtype=np.int64) // nps
+    tbp = float(np.float32(tsamp)) / float(period)
+    frac = np.modf(d * tbp)[0]
+    bins = np.clip(np.floor(frac * nbins), 0, nbins - 1).astype(np.int64)
+    src = np.clip(np.rint(d + af * ((d - h) * (d - h) - h * h)), 0, n - 1).astype(np.int64)
+    hits = np.zeros((nints, nbins), dtype=np.int64)
+    np.add.at(hits, (subint, bins), 1)
+    sums = np.zeros((nints, nsub, nbins), dtype=np.int64)
+    nactive = np.zeros(nsub, dtype=np.int32)
+    for c in np.nonzero(kill)[0]:
+        s = (int(c) * nsub) // nchans
+        nactive[s] += 1
+        np.add.at(sums, (subint, s, bins), values[src + off[c], c].astype(np.int64))
+    return sums, hits.astype(np.int32), nactive

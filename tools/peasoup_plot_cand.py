@@ -4,7 +4,11 @@ CandidatePlotter, tools/peasoup_tools.py:167-412): profile, sub-integrations,
 sub-integration statistics, info table, DM / acceleration / S/N scatters of
 the associated hits, DM-acceleration map, every candidate in period-DM space.
 
-    peasoup_plot_cand.py OUTDIR [INDEX ...] [-o FILE] [--all N] [--predictor]
+    peasoup_plot_cand.py OUTDIR [INDEX ...] [-o FILE] [--all N] [--predictor] [--cubes FILE]
+
+--cubes FILE: a fold-cube file written by ``python -m peasoup_amd cube --overview
+OUTDIR/overview.xml`` (cube i belongs to candidate i); adds the frequency-phase
+and time-phase panels of the filterbank fold.
 """
 import argparse
 import os
@@ -22,13 +26,14 @@ def main() -> int:
     p.add_argument("-o", "--output", default=None, help="file name (one index only)")
     p.add_argument("--all", type=int, default=0, help="plot the first N candidates as Cand%%04d.png")
     p.add_argument("--predictor", action="store_true", help="print each candidate's predictor instead")
+    p.add_argument("--cubes", default=None, help="fold-cube file of the same candidates (adds two panels)")
     a = p.parse_args()
-    if a.all:
+    if a.all and not a.cubes:
         for f in plot_all(a.outdir, a.all):
             print(f)
         return 0
-    pl = CandidatePlotter(a.outdir)
-    for i in a.index or [0]:
+    pl = CandidatePlotter(a.outdir, cubes=a.cubes) if a.cubes else CandidatePlotter(a.outdir)
+    for i in (range(min(a.all, len(pl))) if a.all else a.index or [0]):
         if a.predictor:
             print(pl.overview.make_predictor(i))
             continue
