@@ -23,6 +23,7 @@
 
 #include "psoup/cli.hpp"
 #include "psoup/common.hpp"
+#include "psoup/rfi.hpp"
 
 namespace psoup {
 
@@ -81,7 +82,16 @@ struct SpCmdLineOptions {
   double baseline = 2.0;   // s
   int limit = 1000;
   std::string dedisp_kernel = "auto";
+  // RFI excision before the search (psoup/rfi.hpp); off by default
+  bool rfi = false;
+  bool zero_dm = false;  // implies rfi
+  int rfi_block = 4096;
+  double rfi_thresh = 5.0;
+  double rfi_chan_frac = 0.3;
+  double rfi_block_frac = 0.3;
+  std::string rfi_maskfilename;  // --rfi_mask_out
 };
+RfiParams sp_rfi_params(const SpCmdLineOptions& args);
 // "%Y-%m-%d-%H:%M_spsearch.output" in UTC.
 std::string default_sp_output_filename();
 bool parse_sp_cmdline(SpCmdLineOptions& args, const std::vector<std::string>& argv, bool* exit_now = nullptr);
@@ -168,6 +178,7 @@ struct SpResult {
   std::vector<int> widths;
   uint64_t baseline = 0;
   uint64_t events = 0, reruns = 0;
+  std::string rfi_comment;  // "# rfi: ..." header lines; empty without --rfi
 };
 SpParams sp_params_from(const SpCmdLineOptions& args, double tsamp);
 // Reads the filterbank, dedisperses on min(-t, devices) GPUs (one thread per

@@ -28,7 +28,15 @@ void bind_sp(py::module_& m) {
       .def_readwrite("boxcar_max", &SpCmdLineOptions::boxcar_max)
       .def_readwrite("baseline", &SpCmdLineOptions::baseline)
       .def_readwrite("limit", &SpCmdLineOptions::limit)
-      .def_readwrite("dedisp_kernel", &SpCmdLineOptions::dedisp_kernel);
+      .def_readwrite("dedisp_kernel", &SpCmdLineOptions::dedisp_kernel)
+      .def_readwrite("rfi", &SpCmdLineOptions::rfi)
+      .def_readwrite("zero_dm", &SpCmdLineOptions::zero_dm)
+      .def_readwrite("rfi_block", &SpCmdLineOptions::rfi_block)
+      .def_readwrite("rfi_thresh", &SpCmdLineOptions::rfi_thresh)
+      .def_readwrite("rfi_chan_frac", &SpCmdLineOptions::rfi_chan_frac)
+      .def_readwrite("rfi_block_frac", &SpCmdLineOptions::rfi_block_frac)
+      .def_readwrite("rfi_maskfilename", &SpCmdLineOptions::rfi_maskfilename);
+  m.def("sp_rfi_params", &sp_rfi_params);
   m.def("parse_sp_cmdline", [](const std::vector<std::string>& argv) {
     SpCmdLineOptions a;
     bool exit_now = false;
@@ -113,7 +121,8 @@ void bind_sp(py::module_& m) {
       .def_readwrite("widths", &SpResult::widths)
       .def_readwrite("baseline", &SpResult::baseline)
       .def_readwrite("events", &SpResult::events)
-      .def_readwrite("reruns", &SpResult::reruns);
+      .def_readwrite("reruns", &SpResult::reruns)
+      .def_readwrite("rfi_comment", &SpResult::rfi_comment);
   m.def("run_sp_pipeline", [](const SpCmdLineOptions& a) {
     py::gil_scoped_release nogil;
     return run_sp_pipeline(a);

@@ -121,6 +121,7 @@ SigprocHeader dict_to_header(const py::dict& d) {
 void bind_ffa(py::module_& m);  // bind_ffa.cpp
 void bind_sp(py::module_& m);   // bind_sp.cpp
 void bind_cube(py::module_& m);  // bind_cube.cpp
+void bind_rfi(py::module_& m);   // bind_rfi.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -693,6 +694,7 @@ PYBIND11_MODULE(_C, m) {
   bind_ffa(m);
   bind_sp(m);
   bind_cube(m);
+  bind_rfi(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -1,5 +1,6 @@
 #include "psoup/cli.hpp"
 #include "psoup/foldcube.hpp"
+#include "psoup/rfi.hpp"
 #include "psoup/singlepulse.hpp"
 
 #include <cstdlib>
@@ -360,8 +361,28 @@ bool parse_sp_cmdline(SpCmdLineOptions& a, const std::vector<std::string>& argv,
       val_n("", "baseline", "Length of the trend blocks in seconds", a.baseline),
       val_n("", "limit", "Upper limit on the number of candidates written", a.limit),
       val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
+      sw("", "rfi", "Clean the filterbank first: block-statistics RFI mask", a.rfi),
+      sw("", "zero_dm", "Also subtract the band mean of the unflagged channels (implies --rfi)", a.zero_dm),
+      val_n("", "rfi_block", "RFI block length in samples (a multiple of 256 in [256, 65536])", a.rfi_block),
+      val_n("", "rfi_thresh", "RFI flagging threshold in robust sigmas (1.4826 MAD)", a.rfi_thresh),
+      val_n("", "rfi_chan_frac", "Flag a channel whole above this flagged share of its blocks", a.rfi_chan_frac),
+      val_n("", "rfi_block_frac", "Flag a block whole above this flagged share of its live channels",
+            a.rfi_block_frac),
+      val_s("", "rfi_mask_out", "RFI mask output filename", a.rfi_maskfilename),
   };
-  return run_parser(specs, argv, "Peasoup single-pulse extension - a GPU transient search pipeline", nullptr, exit_now);
+  if (!run_parser(specs, argv, "Peasoup single-pulse extension - a GPU transient search pipeline", nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.zero_dm) a.rfi = true;
+  if (a.rfi_block < 256 || a.rfi_block > 65536 || a.rfi_block % 256 != 0) {
+    std::cerr << "Error: --rfi_block must be a multiple of 256 in [256, 65536]" << std::endl;
+    return false;
+  }
+  if (!(a.rfi_thresh >= 0) || !(a.rfi_chan_frac >= 0) || !(a.rfi_block_frac >= 0)) {
+    std::cerr << "Error: --rfi_thresh, --rfi_chan_frac and --rfi_block_frac must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
 }
 
 std::string default_cube_output_filename() {
@@ -417,6 +438,35 @@ bool parse_cube_cmdline(FoldCubeCmdLineOptions& a, const std::vector<std::string
   a.fold_nsamps = static_cast<uint64_t>(fold_nsamps);
   if (a.top < 1 || a.limit < 0) {
     std::cerr << "Error: --top must be at least 1 and --limit non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+bool parse_rfi_cmdline(RfiCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The cleaned filterbank (header bytes copied verbatim)", a.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_s("", "mask_out", "RFI mask output filename", a.maskfilename),
+      val_s("", "kill_out", "Output killfile: the input mask plus every channel flagged whole", a.killoutfilename),
+      val_n("", "rfi_block", "Block length in samples (a multiple of 256 in [256, 65536])", a.rfi_block),
+      val_n("", "rfi_thresh", "Flagging threshold in robust sigmas (1.4826 MAD)", a.rfi_thresh),
+      val_n("", "rfi_chan_frac", "Flag a channel whole above this flagged share of its blocks", a.rfi_chan_frac),
+      val_n("", "rfi_block_frac", "Flag a block whole above this flagged share of its live channels",
+            a.rfi_block_frac),
+      sw("", "zero_dm", "Subtract the band mean of the unflagged channels from every sample", a.zero_dm),
+      sw("v", "verbose", "verbose mode", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup RFI excision - block-statistics mask and zero-DM filter", nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.rfi_block < 256 || a.rfi_block > 65536 || a.rfi_block % 256 != 0) {
+    std::cerr << "Error: --rfi_block must be a multiple of 256 in [256, 65536]" << std::endl;
+    return false;
+  }
+  if (!(a.rfi_thresh >= 0) || !(a.rfi_chan_frac >= 0) || !(a.rfi_block_frac >= 0)) {
+    std::cerr << "Error: --rfi_thresh, --rfi_chan_frac and --rfi_block_frac must be non-negative" << std::endl;
     return false;
   }
   return true;

@@ -154,6 +154,18 @@ SpParams sp_params_from(const SpCmdLineOptions& a, double tsamp) {
   return p;
 }
 
+RfiParams sp_rfi_params(const SpCmdLineOptions& a) {
+  RfiParams p;
+  PSOUP_CHECK(a.rfi_block > 0, "--rfi_block must be positive");
+  p.block = static_cast<uint64_t>(a.rfi_block);
+  p.thresh = a.rfi_thresh;
+  p.chan_frac = a.rfi_chan_frac;
+  p.block_frac = a.rfi_block_frac;
+  p.zero_dm = a.zero_dm;
+  rfi_check_params(p);
+  return p;
+}
+
 SpResult run_sp_pipeline(const SpCmdLineOptions& args) {
   SpResult res;
   Stopwatch t_total, t_read;
@@ -171,6 +183,39 @@ SpResult run_sp_pipeline(const SpCmdLineOptions& args) {
   PSOUP_CHECK(ndev > 0, "no HIP devices visible");
   const int ngpu = std::max(1, std::min(ndev, args.max_num_threads));
   for (int i = 0; i < ngpu; ++i) res.devices.push_back(i);
+  // --rfi: the packed bytes are cleaned once on device 0 (unpack, block sums,
+  // flags, apply, pack) and the flagged channels join the killmask before the
+  // geometry is made.  Device 0 unpacks the cleaned bytes where they lie; the
+  // other devices get the same bytes from a host copy.
+  const bool rfi = args.rfi || args.zero_dm;
+  DeviceBuffer<uint8_t> d_clean;
+  std::vector<uint8_t> h_clean;
+  if (rfi) {
+    const RfiParams rp = sp_rfi_params(args);
+    const uint64_t bytes = fb.nsamps() * fb.bytes_per_sample();
+    PSOUP_CHECK(fb.nsamps() > 0 && bytes <= fb.data_bytes(), "spsearch: empty or truncated filterbank");
+    PSOUP_HIP_CHECK(hipSetDevice(0));
+    Stream cs;
+    d_clean.resize(bytes);
+    staged_upload(
+        bytes, 64ull << 20, [&](uint64_t off, uint64_t n, uint8_t* dst) { fb.read_data(off, n, dst); }, d_clean.data(),
+        cs.get());
+    PSOUP_HIP_CHECK(hipStreamSynchronize(cs.get()));
+    RfiCleaner cleaner(rp, cs.get());
+    const RfiMask mask = cleaner.clean_packed(d_clean.data(), hdr.nchans, fb.nsamps(), hdr.nbits, kill);
+    for (size_t c = 0; c < kill.size(); ++c) kill[c] = (kill[c] != 0 && mask.killmask[c] != 0) ? 1 : 0;
+    res.rfi_comment = rfi_summary_comment(mask, rp);
+    if (!args.rfi_maskfilename.empty()) {
+      RfiMaskHeader mh;
+      mh.nbits = static_cast<uint32_t>(hdr.nbits);
+      mh.tsamp = hdr.tsamp;
+      write_rfi_mask(args.rfi_maskfilename, mask, rp, mh);
+    }
+    if (ngpu > 1) {
+      h_clean.resize(bytes);
+      PSOUP_HIP_CHECK(hipMemcpy(h_clean.data(), d_clean.data(), bytes, hipMemcpyDeviceToHost));
+    }
+  }
   DedispGeometry geom = DedispGeometry::make(hdr, fb.nsamps(), res.dm_list, kill);
   res.nsamps = geom.out_nsamps;
   res.tsamp = hdr.tsamp;
@@ -195,7 +240,14 @@ SpResult run_sp_pipeline(const SpCmdLineOptions& args) {
       PSOUP_HIP_CHECK(hipSetDevice(dev));
       Stream stream, side;
       DeviceFilterbank dfb(geom, stream.get());
-      load_filterbank_fanout({&dfb}, {dev}, fb);
+      if (!rfi) {
+        load_filterbank_fanout({&dfb}, {dev}, fb);
+      } else if (dev == 0) {
+        dfb.load_packed_device(d_clean.data());
+        PSOUP_HIP_CHECK(hipStreamSynchronize(stream.get()));
+      } else {
+        load_filterbank_fanout({&dfb}, {dev}, h_clean.data());
+      }
       Dedisperser dd(dfb, stream.get());
       dd.warm();  // every table up front: no upload lands between the two streams' work
       PSOUP_HIP_CHECK(hipStreamSynchronize(stream.get()));
@@ -282,6 +334,7 @@ void write_sp_output(const std::string& path, const SpCmdLineOptions& args, cons
                static_cast<unsigned long long>(res.events), static_cast<double>(args.min_snr),
                res.timers.count("searching") ? res.timers.at("searching") : 0.0,
                res.timers.count("total") ? res.timers.at("total") : 0.0);
+  if (!res.rfi_comment.empty()) std::fputs(res.rfi_comment.c_str(), fo);
   std::fprintf(fo, "#%8s %12s %16s %7s %7s %10s %8s %12s %12s %7s %7s\n", "snr", "sample", "time_s", "width", "dm_idx",
                "dm", "members", "first_sample", "last_sample", "dm_lo", "dm_hi");
   for (const SpCandidate& c : res.candidates)

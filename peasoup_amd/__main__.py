@@ -1,7 +1,8 @@
 """``python -m peasoup_amd [peasoup flags]`` (or ``python -m peasoup_amd ffa
 [ffaster flags]`` for the FFA search, ``python -m peasoup_amd sps [spsearch
 flags]`` for the single-pulse search, ``python -m peasoup_amd cube [foldcube
-flags]`` for the filterbank fold cubes of candidates) -- the peasoup CLI as a
+flags]`` for the filterbank fold cubes of candidates, ``python -m peasoup_amd
+clean [rficlean flags]`` for the RFI excision) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -69,6 +70,8 @@ def main(argv=None) -> int:
         return _main_sps(["spsearch"] + argv[2:])
     if len(argv) > 1 and argv[1] == "cube":
         return _main_cube(["foldcube"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "clean":
+        return _main_clean(["rficlean"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -147,6 +150,26 @@ def _main_cube(argv) -> int:
         _fail_hard("cube", e)
     if run is not None and args.verbose:
         print(f"Wrote {run.ncand} fold cubes to {args.outfilename}")
+    return 0
+
+
+def _main_clean(argv) -> int:
+    from . import _C
+    from .models.rfi import clean_filterbank
+
+    ok, exit_now, args = _C.parse_rfi_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        mask = clean_filterbank(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("clean", e)
+    if mask is not None and args.verbose:
+        print(f"RFI excision: {mask.flagged_chans} of {mask.nchans} channels, {mask.flagged_blocks} of {mask.nblk} "
+              f"blocks, {mask.flagged_cells} of {mask.nchans * mask.nblk} cells flagged")
     return 0
 
 

@@ -49,8 +49,21 @@ class RankSinglePulse:
         kill = [1] * int(header["nchans"])
         if args.killfilename:
             kill = list(_C.read_killfile(args.killfilename, int(header["nchans"]))[0])
-        self.geom = _C.DedispGeometry.make(self.header, int(nsamps), self.dm_list, kill)
         self.stream = torch.cuda.current_stream().cuda_stream
+        # --rfi: every rank cleans its own copy of the packed bytes in place
+        # (the stage is deterministic, so the copies stay identical); the
+        # flagged channels join the killmask before the geometry is made
+        self.rfi_mask = None
+        self.rfi_params = None
+        if args.rfi or args.zero_dm:
+            if packed is None or not packed.is_cuda:
+                raise ValueError("--rfi needs the packed filterbank on a HIP device")
+            self.rfi_params = _C.sp_rfi_params(args)
+            cleaner = _C.RfiCleaner(self.rfi_params, self.stream)
+            self.rfi_mask = cleaner.clean_packed(packed.data_ptr(), int(header["nchans"]), int(nsamps),
+                                                 int(header["nbits"]), kill)
+            kill = [int(bool(a) and bool(b)) for a, b in zip(kill, self.rfi_mask.killmask)]
+        self.geom = _C.DedispGeometry.make(self.header, int(nsamps), self.dm_list, kill)
         self.dfb = _C.DeviceFilterbank(self.geom, self.stream)
         if packed is not None:
             if packed.is_cuda:
@@ -124,6 +137,17 @@ def run_single_pulse_search(args, write: bool = True):
     res.widths = list(rs.engine.widths)
     res.baseline = int(rs.engine.baseline)
     res.events = len(events)
+    if rs.rfi_mask is not None:
+        res.rfi_comment = _C.rfi_summary_comment(rs.rfi_mask, rs.rfi_params)
+        if args.rfi_maskfilename:
+            from .rfi import mask_dict
+            from ..utils.outputs import write_rfi_mask
+
+            p = rs.rfi_params
+            write_rfi_mask(args.rfi_maskfilename,
+                           {"nbits": int(header["nbits"]), "zero_dm": p.zero_dm, "nsamps": int(nsamps),
+                            "block": p.block, "tsamp": float(header["tsamp"]), "thresh": p.thresh,
+                            "chan_frac": p.chan_frac, "block_frac": p.block_frac}, mask_dict(rs.rfi_mask))
     if write:
         _C.write_sp_output(args.outfilename, args, res)
     return res

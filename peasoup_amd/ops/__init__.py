@@ -31,9 +31,14 @@ from .core import (  # noqa: F401
     irfft,
     median_scrunch5,
     normalise,
+    pack_transpose,
     quantize_q8,
     r2c_interbin_normalise,
     resample,
+    rfi_apply,
+    rfi_block_sums,
+    rfi_clean,
+    rfi_tile,
     resample_v1,
     rfft,
     running_median,

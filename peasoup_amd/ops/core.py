@@ -516,3 +516,81 @@ def fold_cube(chan_major: torch.Tensor, offsets: torch.Tensor, periods, accels, 
     if ncand:
         folder.fold_offsets(off.numpy(), periods, accels, sums.data_ptr(), hits.data_ptr())
     return sums, hits
+
+
+# ------------------------------------------------------------ RFI excision --
+def _check_rows(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    _check(t, torch.int8, name)
+    if t.dim() != 2 or t.shape[1] % 16 or t.data_ptr() % 16:
+        raise ValueError(f"{name} must be int8 [nchans, stride], 16-byte aligned, stride a multiple of 16")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def rfi_tile() -> int:
+    """Samples per workgroup of the rfi_apply kernel."""
+    return int(_C.rfi_tile())
+
+
+def pack_transpose(chan_major: torch.Tensor, nsamps: int, nbits: int, bias: int = 0) -> torch.Tensor:
+    """int8 [nchans, stride] (value - bias) -> packed SIGPROC bytes (time-major,
+    LSB-first), the inverse of ``unpack_transpose``."""
+    _check(chan_major, torch.int8, "chan_major")
+    nchans, stride = int(chan_major.shape[0]), int(chan_major.shape[1])
+    out = torch.empty(int(nsamps) * nchans * int(nbits) // 8, dtype=torch.uint8, device=chan_major.device)
+    _C.pack_transpose_raw(chan_major.data_ptr(), stride, int(nsamps), nchans, int(nbits), int(bias), out.data_ptr(),
+                          _s())
+    return out
+
+
+def rfi_block_sums(chan_major: torch.Tensor, nsamps: int, block: int, bias: int = 0):
+    """Exact block sums of the raw samples (stored value + ``bias``) of int8
+    rows [nchans, stride]: (S1, S2), each int64 [nchans, ceil(nsamps / block)]
+    (the kernel's uint64; the values are below 2^63)."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    nblk = -(-int(nsamps) // int(block))
+    S1 = torch.empty((nchans, nblk), dtype=torch.int64, device=chan_major.device)
+    S2 = torch.empty_like(S1)
+    _C.rfi_block_sums_raw(chan_major.data_ptr(), stride, nchans, int(nsamps), int(block), int(bias), S1.data_ptr(),
+                          S2.data_ptr(), _s())
+    return S1, S2
+
+
+def _rfi_params(block, thresh, chan_frac, block_frac, zero_dm):
+    return _C.RfiParams(int(block), float(thresh), float(chan_frac), float(block_frac), bool(zero_dm))
+
+
+def rfi_apply(chan_major: torch.Tensor, nsamps: int, nbits: int, mask, block: int, bias: int = 0,
+              zero_dm: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Applies a mask (a ``_C.RfiMask``, or a dict with cell, chan_flag,
+    block_flag, fill, G, nb and killmask as ``utils.reference.rfi_flag``
+    returns) to int8 rows [nchans, stride]: in place, or into ``out`` (same
+    layout rules, own stride).  Returns the tensor written."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    dst = chan_major if out is None else out
+    _, dst_stride = _check_rows(dst, "out")
+    if isinstance(mask, dict):
+        mask = _C.RfiMask(int(nsamps), int(block), mask["chan_flag"], mask["block_flag"], mask["cell"], mask["fill"],
+                          mask["G"], mask["nb"], [int(k) for k in mask["killmask"]])
+    cleaner = _C.RfiCleaner(_rfi_params(block, 0.0, 0.0, 0.0, zero_dm), _s())
+    cleaner.apply(chan_major.data_ptr(), stride, dst.data_ptr(), dst_stride, nchans, int(nsamps), int(nbits),
+                  int(bias), mask)
+    return dst
+
+
+def rfi_clean(chan_major: torch.Tensor, nsamps: int, nbits: int, bias: int = 0, killmask=None, block: int = 4096,
+              thresh: float = 5.0, chan_frac: float = 0.3, block_frac: float = 0.3, zero_dm: bool = False,
+              out: Optional[torch.Tensor] = None):
+    """RFI excision of int8 rows [nchans, stride] (raw sample = stored value +
+    ``bias``): block sums on the device, flags on the host, mask / zero-DM
+    apply on the device, in place or into ``out``.  Integer-exact: equals
+    ``utils.reference.rfi_clean``.  Returns (cleaned tensor, ``_C.RfiMask``)."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    dst_ptr, dst_stride = 0, 0
+    if out is not None:
+        _, dst_stride = _check_rows(out, "out")
+        dst_ptr = out.data_ptr()
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    cleaner = _C.RfiCleaner(_rfi_params(block, thresh, chan_frac, block_frac, zero_dm), _s())
+    mask = cleaner.clean(chan_major.data_ptr(), stride, nchans, int(nsamps), int(nbits), int(bias), kill, dst_ptr,
+                         dst_stride)
+    return (chan_major if out is None else out), mask

@@ -253,3 +253,72 @@ def cube_mean(cand: Dict) -> np.ndarray:
     out = np.zeros(den.shape, dtype=np.float64)
     np.divide(np.asarray(cand["sums"], dtype=np.float64), den, out=out, where=den != 0)
     return out
+
+
+# ---------------------------------------------------------------- RFI mask --
+RFI_MASK_MAGIC = b"PSMASK01"
+_MASK_HEADER = struct.Struct("<8s4I2Q4d")  # magic, nchans nblk nbits zero_dm, nsamps block, tsamp thresh chan_frac block_frac
+MASK_HEADER_FIELDS = ("nchans", "nblk", "nbits", "zero_dm", "nsamps", "block", "tsamp", "thresh", "chan_frac",
+                      "block_frac")
+
+
+def write_rfi_mask(path: str, header: Dict, mask: Dict) -> None:
+    """Writes an RFI mask file byte for byte as the native ``write_rfi_mask``
+    (csrc/src/rfi.cpp): little-endian header ``PSMASK01``, uint32 nchans nblk
+    nbits zero_dm, uint64 nsamps block, double tsamp thresh chan_frac
+    block_frac; then uint8 chan_flag[nchans], block_flag[nblk],
+    cell[nchans][nblk], int32 fill[nchans], G[nblk].  ``header`` needs every
+    field but nchans and nblk; ``mask`` is a dict of those arrays.  Written to
+    a temporary file, then renamed."""
+    import os
+
+    cell = np.ascontiguousarray(mask["cell"], dtype=np.uint8)
+    nchans, nblk = cell.shape
+    cf = np.ascontiguousarray(mask["chan_flag"], dtype=np.uint8)
+    bf = np.ascontiguousarray(mask["block_flag"], dtype=np.uint8)
+    fill = np.ascontiguousarray(mask["fill"], dtype="<i4")
+    G = np.ascontiguousarray(mask["G"], dtype="<i4")
+    if cf.shape != (nchans,) or bf.shape != (nblk,) or fill.shape != (nchans,) or G.shape != (nblk,):
+        raise ValueError("rfi mask: inconsistent shapes")
+    blob = [_MASK_HEADER.pack(RFI_MASK_MAGIC, nchans, nblk, int(header["nbits"]), int(bool(header["zero_dm"])),
+                              int(header["nsamps"]), int(header["block"]), float(header["tsamp"]),
+                              float(header["thresh"]), float(header["chan_frac"]), float(header["block_frac"])),
+            cf.tobytes(), bf.tobytes(), cell.tobytes(), fill.tobytes(), G.tobytes()]
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class RfiMaskFile:
+    """Reader of an RFI mask file (``bin/rficlean`` / ``python -m peasoup_amd
+    clean``): ``header`` and the arrays ``chan_flag``, ``block_flag``, ``cell``,
+    ``fill``, ``G``; ``killmask`` is 0 for a channel without an unflagged cell."""
+
+    def __init__(self, path: str):
+        self.path = path
+        buf = open(path, "rb").read()
+        if len(buf) < _MASK_HEADER.size or buf[:8] != RFI_MASK_MAGIC:
+            raise ValueError(f"{path}: not an RFI mask file")
+        self.header: Dict = dict(zip(MASK_HEADER_FIELDS, _MASK_HEADER.unpack_from(buf, 0)[1:]))
+        nc, nb = self.header["nchans"], self.header["nblk"]
+        if len(buf) != _MASK_HEADER.size + nc + nb + nc * nb + 4 * nc + 4 * nb:
+            raise ValueError(f"{path}: truncated RFI mask file")
+        o = _MASK_HEADER.size
+        self.chan_flag = np.frombuffer(buf, np.uint8, nc, o).copy()
+        o += nc
+        self.block_flag = np.frombuffer(buf, np.uint8, nb, o).copy()
+        o += nb
+        self.cell = np.frombuffer(buf, np.uint8, nc * nb, o).reshape(nc, nb).copy()
+        o += nc * nb
+        self.fill = np.frombuffer(buf, "<i4", nc, o).copy()
+        o += 4 * nc
+        self.G = np.frombuffer(buf, "<i4", nb, o).copy()
+
+    @property
+    def killmask(self) -> List[int]:
+        return [int(k) for k in (self.cell == 0).any(axis=1)]
+
+    def as_dict(self) -> Dict:
+        return {"chan_flag": self.chan_flag, "block_flag": self.block_flag, "cell": self.cell, "fill": self.fill,
+                "G": self.G}

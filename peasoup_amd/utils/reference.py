@@ -493,3 +493,120 @@ def fold_cube(values: np.ndarray, offsets: np.ndarray, period: float, af: float,
         nactive[s] += 1
         np.add.at(sums, (subint, s, bins), values[src + off[c], c].astype(np.int64))
     return sums, hits.astype(np.int32), nactive
+
+
+# ------------------------------------------------------------ RFI excision --
+# NumPy oracles of csrc/include/psoup/rfi.hpp, written from its definition in
+# int64 and float64.
+def rfi_rdiv(a, n):
+    """floor((2a + n) / (2n)) for a >= 0, n > 0 (integers or int64 arrays)."""
+    return (2 * a + n) // (2 * n)
+
+
+def rfi_block_lengths(nsamps: int, block: int) -> np.ndarray:
+    nblk = -(-int(nsamps) // int(block))
+    lens = np.full(nblk, int(block), dtype=np.int64)
+    lens[-1] = int(nsamps) - (nblk - 1) * int(block)
+    return lens
+
+
+def rfi_block_sums(values: np.ndarray, block: int) -> Tuple[np.ndarray, np.ndarray]:
+    """values: raw samples [nchans, nsamps].  Returns (S1, S2) uint64 [nchans, nblk]."""
+    x = np.asarray(values).astype(np.int64)
+    nchans, nsamps = x.shape
+    starts = np.arange(0, nsamps, int(block))
+    S1 = np.add.reduceat(x, starts, axis=1)
+    S2 = np.add.reduceat(x * x, starts, axis=1)
+    return S1.astype(np.uint64), S2.astype(np.uint64)
+
+
+def _rfi_outliers(x: np.ndarray, thresh: float) -> Tuple[np.ndarray, float]:
+    med = float(np.median(x))
+    dev = np.abs(x - med)
+    mad = float(np.median(dev))
+    if mad == 0.0:
+        return x != med, med
+    return dev > (thresh * 1.4826) * mad, med
+
+
+def rfi_flag(S1: np.ndarray, S2: np.ndarray, nsamps: int, block: int, killmask=None, thresh: float = 5.0,
+             chan_frac: float = 0.3, block_frac: float = 0.3) -> Dict:
+    """The host step: dict(chan_flag, block_flag, cell uint8; fill, G, nb int32;
+    killmask int list), from the raw block sums [nchans, nblk]."""
+    S1 = np.asarray(S1).astype(np.int64)
+    S2 = np.asarray(S2).astype(np.int64)
+    nchans, nblk = S1.shape
+    lens = rfi_block_lengths(nsamps, block)
+    assert lens.size == nblk
+    live = np.ones(nchans, dtype=bool) if killmask is None or len(killmask) == 0 else np.asarray(killmask) != 0
+    mean = S1.astype(np.float64) / lens.astype(np.float64)
+    var = (lens * S2 - S1 * S1).astype(np.float64) / (lens * lens).astype(np.float64)
+    pre = np.zeros((nchans, nblk), dtype=bool)
+    for c in range(nchans):
+        if not live[c]:
+            pre[c] = True
+            continue
+        fm, _ = _rfi_outliers(mean[c], thresh)
+        fv, med_v = _rfi_outliers(var[c], thresh)
+        pre[c] = fm | fv
+        if med_v == 0.0:
+            pre[c] = True
+    chan_flag = ~live
+    block_flag = np.zeros(nblk, dtype=bool)
+    for c in range(nchans):
+        if live[c] and float(pre[c].sum()) / float(nblk) > chan_frac:
+            chan_flag[c] = True
+    nlive = int(live.sum())
+    if nlive:
+        for b in range(nblk):
+            if float(pre[live, b].sum()) / float(nlive) > block_frac:
+                block_flag[b] = True
+    cell = pre | chan_flag[:, None] | block_flag[None, :]
+    fill = np.zeros(nchans, dtype=np.int64)
+    kill = np.ones(nchans, dtype=np.int64)
+    for c in range(nchans):
+        ok = ~cell[c]
+        n = int(lens[ok].sum())
+        if n:
+            fill[c] = rfi_rdiv(int(S1[c][ok].sum()), n)
+        if n == 0 or not live[c]:
+            kill[c] = 0
+    G = np.zeros(nblk, dtype=np.int64)
+    nb = np.zeros(nblk, dtype=np.int64)
+    for b in range(nblk):
+        ok = ~cell[:, b]
+        nb[b] = int(ok.sum())
+        if nb[b]:
+            G[b] = rfi_rdiv(int(fill[ok].sum()), int(nb[b]))
+    return {"chan_flag": chan_flag.astype(np.uint8), "block_flag": block_flag.astype(np.uint8),
+            "cell": cell.astype(np.uint8), "fill": fill.astype(np.int32), "G": G.astype(np.int32),
+            "nb": nb.astype(np.int32), "killmask": [int(k) for k in kill]}
+
+
+def rfi_apply(values: np.ndarray, mask: Dict, block: int, nbits: int, zero_dm: bool = False) -> np.ndarray:
+    """Step 4 on raw samples [nchans, nsamps]; returns the cleaned raw samples (int64)."""
+    x = np.asarray(values).astype(np.int64)
+    nchans, nsamps = x.shape
+    V = (1 << int(nbits)) - 1
+    cell = np.asarray(mask["cell"]) != 0
+    fill = np.asarray(mask["fill"]).astype(np.int64)
+    G = np.asarray(mask["G"]).astype(np.int64)
+    y = x.copy()
+    for b in range(cell.shape[1]):
+        sl = slice(b * int(block), min(nsamps, (b + 1) * int(block)))
+        ok = ~cell[:, b]
+        n = int(ok.sum())
+        if zero_dm and n:
+            Z = x[ok, sl].sum(axis=0)
+            zbar = rfi_rdiv(Z, n)
+            y[ok, sl] = np.clip(x[ok, sl] - zbar[None, :] + G[b], 0, V)
+        y[~ok, sl] = fill[~ok, None]
+    return y
+
+
+def rfi_clean(values: np.ndarray, block: int, nbits: int, killmask=None, thresh: float = 5.0, chan_frac: float = 0.3,
+              block_frac: float = 0.3, zero_dm: bool = False) -> Tuple[np.ndarray, Dict]:
+    """The whole chain on raw samples [nchans, nsamps]: (cleaned, mask dict)."""
+    S1, S2 = rfi_block_sums(values, block)
+    mask = rfi_flag(S1, S2, values.shape[1], block, killmask, thresh, chan_frac, block_frac)
+    return rfi_apply(values, mask, block, nbits, zero_dm), mask

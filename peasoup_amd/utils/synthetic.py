@@ -37,16 +37,52 @@ class BurstSpec:
     amplitude: float = 1.0      # peak in units of the per-channel noise sigma
 
 
+@dataclass
+class RfiSpec:
+    """Interference: ``channel`` multiplies the noise of ``channel`` by
+    ``amplitude`` throughout; ``impulse`` adds ``amplitude`` sigma to every
+    channel at the same samples (DM 0) from ``time`` for ``duration`` seconds
+    (at least one sample); ``cell`` does that to ``channel`` alone."""
+    kind: str = "impulse"       # "channel" | "impulse" | "cell"
+    channel: int = 0
+    time: float = 0.0           # s
+    duration: float = 0.0       # s
+    amplitude: float = 1.0
+
+
+def _apply_rfi(x: np.ndarray, rfi, t0: int, tsamp: float, noise_only: bool) -> None:
+    """In place on the chunk x [t1 - t0, nchans] of unit-sigma floats."""
+    for r in rfi:
+        if r.kind == "channel":
+            if noise_only:
+                x[:, r.channel] *= np.float32(r.amplitude)
+            continue
+        if noise_only:
+            continue
+        if r.kind not in ("impulse", "cell"):
+            raise ValueError(f"RfiSpec.kind must be channel, impulse or cell, got {r.kind!r}")
+        s0 = int(round(r.time / tsamp))
+        s1 = max(s0 + 1, int(round((r.time + r.duration) / tsamp)))
+        a, b = max(s0 - t0, 0), min(s1 - t0, x.shape[0])
+        if a < b:
+            if r.kind == "impulse":
+                x[a:b, :] += np.float32(r.amplitude)
+            else:
+                x[a:b, r.channel] += np.float32(r.amplitude)
+
+
 def make_header(nchans: int = 64, nbits: int = 2, tsamp: float = 320e-6, fch1: float = 1510.0,
                 foff: float = -1.09, nsamples: int = 0, source_name: str = "synthetic") -> Dict:
     return {"source_name": source_name, "tsamp": tsamp, "fch1": fch1, "foff": foff, "nchans": nchans,
             "nbits": nbits, "nifs": 1, "data_type": 1, "tstart": 50000.0, "nsamples": nsamples}
 
 
-def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 1 << 16, bursts=()) -> np.ndarray:
+def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 1 << 16, bursts=(),
+             rfi=()) -> np.ndarray:
     """Return [nsamps, nchans] uint8 quantised samples (values < 2^nbits).
     ``bursts``: :class:`BurstSpec` pulses, dispersed like the pulsars (they
-    draw nothing from the generator: the noise is the same with or without)."""
+    draw nothing from the generator: the noise is the same with or without).
+    ``rfi``: :class:`RfiSpec` interference, likewise without a draw."""
     rng = np.random.default_rng(seed)
     nchans = int(header["nchans"])
     nbits = int(header["nbits"])
@@ -62,6 +98,7 @@ def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 
     for t0 in range(0, nsamps, chunk):
         t1 = min(nsamps, t0 + chunk)
         x = rng.standard_normal((t1 - t0, nchans)).astype(np.float32)
+        _apply_rfi(x, rfi, t0, tsamp, True)
         t = (np.arange(t0, t1, dtype=np.float64) * tsamp)[:, None]
         for p in pulsars:
             delay = 4.15e3 * p.dm * (1.0 / freqs ** 2 - 1.0 / fch1 ** 2)  # seconds
@@ -78,21 +115,23 @@ def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 
             d = t - delay[None, :] - b.time
             w = b.width / 2.3548
             x += b.amplitude * np.exp(-0.5 * (d / w) ** 2).astype(np.float32)
+        _apply_rfi(x, rfi, t0, tsamp, False)
         q = np.rint(mean + sigma * x)
         out[t0:t1] = np.clip(q, 0, levels).astype(np.uint8)
     return out
 
 
-def write(path: str, nsamps: int, header: Optional[Dict] = None, pulsars=(), seed: int = 0, bursts=()) -> Dict:
+def write(path: str, nsamps: int, header: Optional[Dict] = None, pulsars=(), seed: int = 0, bursts=(),
+          rfi=()) -> Dict:
     hdr = dict(header or make_header())
     hdr["nsamples"] = nsamps
-    vals = generate(nsamps, hdr, pulsars, seed, bursts=bursts)
+    vals = generate(nsamps, hdr, pulsars, seed, bursts=bursts, rfi=rfi)
     write_filterbank(path, hdr, vals)
     return hdr
 
 
-def packed(nsamps: int, header: Dict, pulsars=(), seed: int = 0, bursts=()) -> np.ndarray:
-    return pack_samples(generate(nsamps, header, pulsars, seed, bursts=bursts), int(header["nbits"]))
+def packed(nsamps: int, header: Dict, pulsars=(), seed: int = 0, bursts=(), rfi=()) -> np.ndarray:
+    return pack_samples(generate(nsamps, header, pulsars, seed, bursts=bursts, rfi=rfi), int(header["nbits"]))
 
 
 def generate_packed_torch(nsamps: int, header: Dict, pulsars=(), seed: int = 0, device=None,
