@@ -911,6 +911,20 @@ PYBIND11_MODULE(_C, m) {
     kern::ffa_detrend(P<const uint8_t>(in), n, window, P<unsigned long long>(sums), P<float>(means), P<float>(out),
                       S(s));
   });
+  // the two halves of the raw fold (test access: FoldEngine runs them back to back)
+  k.def("fold_accumulate", [](uintptr_t in, uint64_t n, uintptr_t jobs, int njobs, int nbins, int nints, int chunk,
+                              uintptr_t psum, uintptr_t pcount, uintptr_t s) {
+    PSOUP_CHECK(chunk >= 1, "fold_accumulate: chunk must be positive");
+    PSOUP_CHECK(nints >= 1, "fold_accumulate: nints must be positive");
+    kern::fold_accumulate(P<const float>(in), n, P<const kern::FoldJob>(jobs), njobs, nbins, nints, chunk,
+                          P<float>(psum), P<int32_t>(pcount), S(s));
+  });
+  k.def("fold_reduce", [](uintptr_t psum, uintptr_t pcount, int njobs, int nbins, int nints, int nchunk,
+                          uintptr_t fold, uintptr_t s) {
+    kern::fold_reduce(P<const float>(psum), P<const int32_t>(pcount), njobs, nbins, nints, nchunk, P<float>(fold),
+                      S(s));
+  });
+  k.attr("fold_job_size") = sizeof(kern::FoldJob);  // packed (f8 tsamp_by_period, f8 af, u8 series)
   k.def("fold_shift_table", [](uintptr_t table, int nbins, int nints, uintptr_t s) {
     kern::fold_shift_table(P<float2>(table), nbins, nints, S(s));
   });

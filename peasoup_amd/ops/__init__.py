@@ -21,6 +21,7 @@ from .core import (  # noqa: F401
     fft4_resample_spectrum,
     fold_cube,
     fold_optimise,
+    fold_raw,
     fold_series,
     form_amplitude,
     form_interbin,

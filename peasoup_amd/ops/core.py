@@ -4,6 +4,7 @@ from __future__ import annotations
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .. import _C
@@ -418,19 +419,86 @@ def fold_series(series: torch.Tensor, periods: Sequence[float], accels: Sequence
     return fe.fold_series(series.data_ptr(), [float(p) for p in periods], [float(a) for a in accels])
 
 
-def fold_optimise(folds: torch.Tensor):
-    """Fused fold optimiser on [nfold, 16, 64] folds -> (opt_int[nfold,3], opt_fold, opt_prof)."""
+FOLD_JOB_DTYPE = [("tsamp_by_period", "<f8"), ("af", "<f8"), ("series", "<u8")]  # kern::FoldJob
+_POISON = 0x7FC0DEAD  # a NaN as float32: an element the kernel skipped compares unequal to everything
+
+
+def _guarded(rows: int, shape: tuple, device) -> torch.Tensor:
+    """int32 [rows + 2, *shape] filled with _POISON: rows 1..rows are the
+    payload, rows 0 and rows + 1 the guards."""
+    return torch.full((rows + 2,) + tuple(shape), _POISON, dtype=torch.int32, device=device)
+
+
+def _check_guards(buf: torch.Tensor, name: str) -> None:
+    if not (bool((buf[0] == _POISON).all()) and bool((buf[-1] == _POISON).all())):
+        raise RuntimeError(f"{name}: a guard row was overwritten")
+
+
+def fold_raw(series: torch.Tensor, jobs, nbins: int = 64, nints: int = 16, chunk: Optional[int] = None):
+    """The raw fold (fold_accumulate + fold_reduce) of a batch of series
+    [nseries, n] for ``jobs``: (tsamp_by_period, af, series) records
+    (FOLD_JOB_DTYPE, or a sequence of such triples).  Returns (psum float32
+    [nj, nints, nchunk, nbins], pcount int32 likewise, fold float32 [nj, nints,
+    nbins]).  chunk None is FoldEngine's min(4096, n // nints).  Each output
+    lies between two poisoned guard rows; a changed guard raises."""
+    _check(series, torch.float32, "series")
+    if series.dim() != 2:
+        raise ValueError("series must be [nseries, n]")
+    nseries, n = int(series.shape[0]), int(series.shape[1])
+    jobs = np.ascontiguousarray(np.asarray([tuple(j) for j in jobs], dtype=FOLD_JOB_DTYPE)
+                                if not isinstance(jobs, np.ndarray) else jobs.astype(FOLD_JOB_DTYPE))
+    if jobs.dtype.itemsize != K.fold_job_size:
+        raise RuntimeError("FOLD_JOB_DTYPE does not match kern::FoldJob")
+    nj = int(jobs.shape[0])
+    if nj == 0:
+        raise ValueError("fold_raw: no jobs")
+    if int(jobs["series"].max()) >= nseries:
+        raise ValueError("fold_raw: a job indexes a series past the batch")
+    if nints < 1 or n < nints:
+        raise ValueError("fold_raw: series shorter than nints")
+    if chunk is None:
+        chunk = min(4096, n // nints)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("fold_raw: chunk must be positive")
+    if nbins < 1:
+        raise ValueError("fold_raw: nbins must be positive")  # the launcher refuses nbins > 64
+    nps = n // nints
+    nchunk = (nps + chunk - 1) // chunk
+    dev = series.device
+    d_jobs = torch.from_numpy(jobs.view(np.uint8).reshape(nj, -1).copy()).to(dev)
+    psum = _guarded(nj, (nints, nchunk, nbins), dev)
+    pcount = _guarded(nj, (nints, nchunk, nbins), dev)
+    fold = _guarded(nj, (nints, nbins), dev)
+    K.fold_accumulate(series.data_ptr(), n, d_jobs.data_ptr(), nj, nbins, nints, chunk, psum[1].data_ptr(),
+                      pcount[1].data_ptr(), _s())
+    K.fold_reduce(psum[1].data_ptr(), pcount[1].data_ptr(), nj, nbins, nints, nchunk, fold[1].data_ptr(), _s())
+    for buf, name in ((psum, "psum"), (pcount, "pcount"), (fold, "fold")):
+        _check_guards(buf, "fold_raw " + name)
+    return psum[1:-1].view(torch.float32), pcount[1:-1], fold[1:-1].view(torch.float32)
+
+
+def fold_optimise(folds: torch.Tensor, return_val: bool = False):
+    """Fused fold optimiser on [nfold, 16, 64] folds -> (opt_int[nfold,3], opt_fold, opt_prof), with
+    ``return_val`` also opt_val[nfold] (the winning |S| / sqrt(width)).  Every
+    output lies between two poisoned guard rows; a changed guard raises."""
     _check(folds, torch.float32, "folds")
+    if folds.dim() != 3 or tuple(folds.shape[1:]) != (16, 64):
+        raise ValueError("folds must be [nfold, 16, 64]")
     nf = folds.shape[0]
     dev = folds.device
     table = torch.empty((64, 16, 64), dtype=torch.complex64, device=dev)
     K.fold_shift_table(table.data_ptr(), 64, 16, _s())
-    of = torch.empty_like(folds)
-    op = torch.empty((nf, 64), dtype=torch.float32, device=dev)
-    oi = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-    ov = torch.empty(nf, dtype=torch.float32, device=dev)
-    K.fold_optimise(folds.data_ptr(), nf, table.data_ptr(), of.data_ptr(), op.data_ptr(), oi.data_ptr(), ov.data_ptr(), _s())
-    return oi, of, op
+    of = _guarded(nf, (16, 64), dev)
+    op = _guarded(nf, (64,), dev)
+    oi = _guarded(nf, (3,), dev)
+    ov = _guarded(nf, (), dev)
+    K.fold_optimise(folds.data_ptr(), nf, table.data_ptr(), of[1].data_ptr(), op[1].data_ptr(), oi[1].data_ptr(),
+                    ov[1:].data_ptr(), _s())
+    for buf, name in ((of, "opt_fold"), (op, "opt_prof"), (oi, "opt_int"), (ov, "opt_val")):
+        _check_guards(buf, "fold_optimise " + name)
+    out = (oi[1:-1], of[1:-1].view(torch.float32), op[1:-1].view(torch.float32))
+    return out + (ov[1:-1].view(torch.float32),) if return_val else out
 
 
 # ----------------------------------------------------------- coincidence ----

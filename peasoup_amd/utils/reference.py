@@ -8,7 +8,7 @@ the algorithm on tutorial.fil without a GPU.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -235,19 +235,39 @@ def spectrum_peaks(series: np.ndarray, af: float, mean: float, std: float, n: in
 
 
 # ---------------------------------------------------------------- folding --
-def fold_series(x: np.ndarray, period: float, tsamp: float, nbins: int = 64, nints: int = 16) -> np.ndarray:
-    """fold_time_series_kernel (kernels.cu:597-633): counts start at 1."""
-    n = len(x)
+def fold_indices(n: int, tsamp_by_period: float, af: float, nbins: int = 64, nints: int = 16):
+    """Per folded sample j < (n // nints) * nints: (subint, phase bin, source
+    index, phase in [0, 1), unrounded source position), all from float64.
+    The source is the v1 resampler's (resample_v1), clamped to [0, n - 1]."""
     nps = n // nints
-    out = np.zeros((nints, nbins), np.float64)
-    cnt = np.ones((nints, nbins), np.int64)
     j = np.arange(nps * nints, dtype=np.float64)
-    ph = np.modf(j * (tsamp / period))[0]
+    ph = np.modf(j * tsamp_by_period)[0]
     b = np.floor(ph * nbins).astype(np.int64)
-    s = (np.arange(nps * nints) // nps)
-    np.add.at(out, (s, b), x[: nps * nints].astype(np.float64))
+    s = np.arange(nps * nints) // nps
+    h = n / 2.0
+    pos = j + af * ((j - h) ** 2 - h * h)
+    src = np.clip(np.rint(pos), 0, n - 1).astype(np.int64)
+    return s, b, src, ph, pos
+
+
+def fold_sums(x: np.ndarray, tsamp_by_period: float, af: float, nbins: int = 64, nints: int = 16):
+    """The raw fold of one job (fold.hip fold_accumulate): sums float64
+    [nints, nbins] and counts int64 [nints, nbins] (from 0) of the resampled
+    series x[src(j)] over the samples j of each subint and phase bin."""
+    s, b, src, _, _ = fold_indices(len(x), tsamp_by_period, af, nbins, nints)
+    out = np.zeros((nints, nbins), np.float64)
+    cnt = np.zeros((nints, nbins), np.int64)
+    np.add.at(out, (s, b), x[src].astype(np.float64))
     np.add.at(cnt, (s, b), 1)
-    return (out / cnt).astype(np.float32)
+    return out, cnt
+
+
+def fold_series(x: np.ndarray, period: float, tsamp: float, nbins: int = 64, nints: int = 16,
+                af: float = 0.0) -> np.ndarray:
+    """fold_time_series_kernel (kernels.cu:597-633): counts start at 1.  af
+    (accel_factor) folds the v1-resampled series, as the fused fold kernel."""
+    out, cnt = fold_sums(x, tsamp / period, af, nbins, nints)
+    return (out / (cnt + 1)).astype(np.float32)
 
 
 def shift_table(nbins: int = 64, nints: int = 16) -> np.ndarray:
@@ -285,6 +305,52 @@ def fold_optimise(fold: np.ndarray, nbins: int = 64, nints: int = 16):
     return t, s, j, opt_fold, opt_prof
 
 
+def fold_optimise_cube(fold: np.ndarray, nbins: int = 64, nints: int = 16) -> np.ndarray:
+    """The float32 magnitude cube [template][shift][bin] whose argmax
+    fold_optimise returns (its complex64 arithmetic, before the cast)."""
+    F = np.fft.fft(fold.astype(np.complex64), axis=1)
+    prof = (F[None, :, :] * shift_table(nbins, nints)).sum(axis=1)
+    ntmpl = nbins - 1
+    box = (np.arange(nbins)[None, :] <= np.arange(ntmpl)[:, None]).astype(np.complex64)
+    T = np.fft.fft(box, axis=1)
+    arr = prof[None, :, :] * T[:, None, :] / np.sqrt(np.arange(1, ntmpl + 1, dtype=np.float32))[:, None, None]
+    arr[:, :, 0] = 0
+    return np.abs(np.fft.ifft(arr, axis=2) * nbins)
+
+
+def fold_optimise64(fold: np.ndarray, nbins: int = 64, nints: int = 16, shift: Optional[int] = None):
+    """fold_optimise in complex128: the shift phases stay the float32 values
+    of shift_table (they define the operation), everything after them is
+    float64.  Returns (opt_template, opt_shift, opt_bin_raw, opt_fold float64,
+    opt_prof float64, mag float64 [nbins - 1, nbins, nbins]); opt_fold and
+    opt_prof are evaluated at ``shift`` when given, else at opt_shift."""
+    F = np.fft.fft(fold.astype(np.float64), axis=1)
+    two_pi = np.float32(2 * 3.14159265359)
+    sv = np.arange(nbins)[:, None, None]
+    iv = np.arange(nints)[None, :, None].astype(np.float32)
+    bv = np.arange(nbins)[None, None, :]
+    sf = (iv / np.float32(nints)) * (sv - nbins // 2).astype(np.float32)
+    ramp = (bv.astype(np.float32) * two_pi / np.float32(nbins)).astype(np.float32)
+    ramp = np.where(bv > nbins // 2, ramp - two_pi, ramp).astype(np.float32)
+    sh = np.exp(1j * (-1.0 * ramp * sf).astype(np.float32).astype(np.float64))
+    post = F[None, :, :] * sh                      # [shift][int][bin]
+    prof = post.sum(axis=1)                        # [shift][bin]
+    ntmpl = nbins - 1
+    box = (np.arange(nbins)[None, :] <= np.arange(ntmpl)[:, None]).astype(np.float64)
+    T = np.fft.fft(box, axis=1)                    # [template][bin]
+    arr = prof[None, :, :] * T[:, None, :] / np.sqrt(np.arange(1, ntmpl + 1, dtype=np.float64))[:, None, None]
+    arr[:, :, 0] = 0
+    mag = np.abs(np.fft.ifft(arr, axis=2) * nbins)
+    am = int(np.argmax(mag))
+    t = am // (nbins * nbins)
+    s = (am // nbins) % nbins
+    j = am % nbins
+    at = s if shift is None else int(shift)
+    opt_fold = (np.fft.ifft(post[at], axis=1) * nbins).real
+    opt_prof = (np.fft.ifft(prof[at]) * nbins).real
+    return t, s, j, opt_fold, opt_prof, mag
+
+
 def calculate_sn(prof: np.ndarray, bin: int, width: int) -> Tuple[float, float]:
     nbins = len(prof)
     edge = int(width * 0.3 + 0.5)
@@ -294,16 +360,18 @@ def calculate_sn(prof: np.ndarray, bin: int, width: int) -> Tuple[float, float]:
     up, lo = b + (wb2 + edge), b - (wb2 + edge)
     on = np.array([rprof[i] for i in range(nbins) if lo <= i <= up], np.float32)
     off = np.array([rprof[i] for i in range(nbins) if not (lo <= i <= up)], np.float32)
+    # an empty off-pulse set (wide templates) has mean NaN, as the native code
     on_mean = np.float32(on.astype(np.float64).sum() / len(on))
-    off_mean = np.float32(off.astype(np.float64).sum() / len(off))
+    off_mean = np.float32(off.astype(np.float64).sum() / len(off)) if len(off) else np.float32(np.nan)
     acc = np.float32(0)
     for v in off:
         acc = np.float32(float(acc) + (float(v) - float(off_mean)) ** 2)
-    off_std = np.sqrt(acc / np.float32(len(off)))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        sn1 = np.float32((on_mean - off_mean) * math.sqrt(width) / off_std)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        off_std = np.sqrt(acc / np.float32(len(off)))
+        sn1 = np.float32(np.float64(on_mean - off_mean) * math.sqrt(width) / np.float64(off_std))
         r = ((rprof - off_mean) / off_std).astype(np.float32)
-        sn2 = np.float32(r.astype(np.float64).sum() / math.sqrt(width)) if width > 0 else np.float32(np.inf)
+        # width 0 divides by zero: +-inf or NaN by the sign of the sum
+        sn2 = np.float32(np.float64(r.astype(np.float64).sum()) / np.float64(math.sqrt(width)))
     if sn1 > 99999:
         sn1 = np.float32(0)
     if sn2 > 99999:

@@ -505,22 +505,22 @@ def test_fft4_resample_spectrum_matches_numpy(log2n, fft4_flags):
 
 
 def test_fold_optimise_matches_fft_reference():
-    from peasoup_amd import ops
+    """The six folds of this test (three drifting pulses, three of noise) are
+    the last six of test_fold_gpu's sweep; all six, the noise ones included,
+    are held to its rule (check_optimise) against the complex128 oracle."""
+    import test_fold_gpu as tf
 
-    rng = np.random.default_rng(9)
-    folds = rng.standard_normal((6, 16, 64)).astype(np.float32)
-    # add a drifting narrow pulse to some folds
-    for f in range(3):
-        for i in range(16):
-            folds[f, i, (20 + (i * (f + 1)) // 4) % 64] += 8.0
-    oi, of, op = ops.fold_optimise(torch.from_numpy(folds).to(dev))
-    oi, of, op = oi.cpu().numpy(), of.cpu().numpy(), op.cpu().numpy()
-    for f in range(6):
-        t, s, j, ofold, oprof = ref.fold_optimise(folds[f])
-        if f < 3:
-            assert (oi[f, 0], oi[f, 1], oi[f, 2]) == (t, s, j)
-            assert np.allclose(of[f], ofold, rtol=1e-3, atol=1e-2)
-            assert np.allclose(op[f], oprof, rtol=1e-3, atol=1e-2)
+    folds, kinds = tf.optimise_sweep()
+    ks = list(range(len(folds) - 6, len(folds)))
+    assert [kinds[k] for k in ks] == ["pulse"] * 3 + ["noise"] * 3
+    oi, of, op, ov = tf.run_optimise(folds[ks])
+    for r, k in enumerate(ks):
+        check = ref.fold_optimise(folds[k])
+        if kinds[k] == "pulse":  # what this test has always asserted
+            assert (oi[r, 0], oi[r, 1], oi[r, 2]) == check[:3]
+            assert np.allclose(of[r], check[3], rtol=1e-3, atol=1e-2)
+            assert np.allclose(op[r], check[4], rtol=1e-3, atol=1e-2)
+        tf.check_optimise(folds[k], k, oi[r], of[r], op[r], ov[r])
 
 
 def test_fold_series_against_reference(C):
