@@ -122,6 +122,7 @@ void bind_ffa(py::module_& m);  // bind_ffa.cpp
 void bind_sp(py::module_& m);   // bind_sp.cpp
 void bind_cube(py::module_& m);  // bind_cube.cpp
 void bind_rfi(py::module_& m);   // bind_rfi.cpp
+void bind_burst(py::module_& m); // bind_burst.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -695,6 +696,7 @@ PYBIND11_MODULE(_C, m) {
   bind_sp(m);
   bind_cube(m);
   bind_rfi(m);
+  bind_burst(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -1,4 +1,5 @@
 #include "psoup/cli.hpp"
+#include "psoup/burstcube.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
 #include "psoup/singlepulse.hpp"
@@ -438,6 +439,62 @@ bool parse_cube_cmdline(FoldCubeCmdLineOptions& a, const std::vector<std::string
   a.fold_nsamps = static_cast<uint64_t>(fold_nsamps);
   if (a.top < 1 || a.limit < 0) {
     std::cerr << "Error: --top must be at least 1 and --limit non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_burst_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_burstcube.bursts", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_burst_cmdline(BurstCubeCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_burst_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_s("", "spfile", "Candidates: an spsearch output (S/N, sample, width and DM columns)", a.spfilename),
+      val_s("", "candfile", "Candidates: one 'sample width dm [snr]' per line, '#' comments", a.candfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_n("", "ntime", "Time bins per cutout (1..1024)", a.ntime),
+      val_n("", "nsub", "Subbands of the waterfall (1..nchans; capped at nchans)", a.nsub),
+      val_n("", "ndm", "DM rows of the DM-time plane (1..1024)", a.ndm),
+      val_n("", "tscrunch", "Samples per time bin (0 = half the candidate's width, at least 1; at most 4096)",
+            a.tscrunch),
+      val_n("", "dm_half_range", "DM rows span the candidate's DM -/+ this (0 = the DM itself: rows span 0..2 DM)",
+            a.dm_half_range),
+      val_n("", "limit", "At most this many candidates from the top of the list", a.limit),
+      sw("v", "verbose", "verbose mode", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup burst-cutout extension - dedispersed waterfall and DM-time plane per pulse",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.spfilename.empty() == a.candfilename.empty()) {
+    std::cerr << "Error: give exactly one of --spfile and --candfile" << std::endl;
+    return false;
+  }
+  if (a.ntime < 1 || a.ntime > 1024) {
+    std::cerr << "Error: --ntime must be in 1..1024" << std::endl;
+    return false;
+  }
+  if (a.ndm < 1 || a.ndm > 1024) {
+    std::cerr << "Error: --ndm must be in 1..1024" << std::endl;
+    return false;
+  }
+  if (a.nsub < 1) {
+    std::cerr << "Error: --nsub must be at least 1" << std::endl;
+    return false;
+  }
+  if (a.tscrunch < 0 || a.tscrunch > 4096) {
+    std::cerr << "Error: --tscrunch must be in 0..4096" << std::endl;
+    return false;
+  }
+  if (!(a.dm_half_range >= 0) || a.limit < 0) {
+    std::cerr << "Error: --dm_half_range and --limit must be non-negative" << std::endl;
     return false;
   }
   return true;

@@ -19,6 +19,7 @@ from .core import (  # noqa: F401
     spec_unblock,
     spec_pblk_index,
     fft4_resample_spectrum,
+    burst_cube,
     fold_cube,
     fold_optimise,
     fold_raw,

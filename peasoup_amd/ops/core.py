@@ -586,6 +586,51 @@ def fold_cube(chan_major: torch.Tensor, offsets: torch.Tensor, periods, accels, 
     return sums, hits
 
 
+# ----------------------------------------------------------- burst cutouts --
+def burst_cube(chan_major: torch.Tensor, ds_offsets: torch.Tensor, dmt_offsets: torch.Tensor, samples, tscrunch,
+               ntime: int = 256, nsub: int = 256, bias: int = 0, killmask=None, nsamps: int = None,
+               batch_bytes: int = None):
+    """Cuts time-scrunched, dedispersed sums out of the channel-major int8
+    filterbank ``chan_major`` [nchans, stride] (raw sample = stored value +
+    ``bias``; stride a multiple of 16; the first ``nsamps`` samples of a row
+    are valid, default all).  Per candidate: ``ds_offsets`` int32 [ncand,
+    nchans] (the waterfall's offsets), ``dmt_offsets`` int32 [ncand, ndm,
+    nchans] (one row of offsets per DM row), ``samples`` the first sample t0
+    of time bin 0 (may be negative) and ``tscrunch`` the samples f per time
+    bin (one int for all, or one per candidate).  Returns (ds_sums, ds_hits)
+    int32 [ncand, nsub, ntime] and (dmt_sums, dmt_hits) int32 [ncand, ndm,
+    ntime] as four tensors: exactly the NumPy oracle's
+    (utils.reference.burst_cube_offsets).  Every candidate is validated before
+    anything is launched (``NativeError`` naming the candidate)."""
+    _check(chan_major, torch.int8, "chan_major")
+    if chan_major.dim() != 2:
+        raise ValueError("chan_major must be [nchans, stride]")
+    nchans, stride = int(chan_major.shape[0]), int(chan_major.shape[1])
+    ds = ds_offsets.detach().to("cpu", torch.int32).contiguous()
+    dmt = dmt_offsets.detach().to("cpu", torch.int32).contiguous()
+    t0 = [int(t) for t in samples]
+    ncand = len(t0)
+    fs = [int(tscrunch)] * ncand if isinstance(tscrunch, int) else [int(f) for f in tscrunch]
+    if ds.dim() != 2 or tuple(ds.shape) != (ncand, nchans) or dmt.dim() != 3 or dmt.shape[0] != ncand or \
+            dmt.shape[2] != nchans or len(fs) != ncand:
+        raise ValueError("ds_offsets must be [ncand, nchans], dmt_offsets [ncand, ndm, nchans]; samples and tscrunch "
+                         "of length ncand")
+    ndm = int(dmt.shape[1])
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    params = _C.BurstParams(int(ntime), int(nsub), ndm)
+    kw = {} if batch_bytes is None else {"batch_bytes": int(batch_bytes)}
+    cutter = _C.BurstCutter(chan_major.data_ptr(), stride, stride if nsamps is None else int(nsamps), nchans,
+                            int(bias), [], kill, params, _s(), **kw)
+    rows = int(nsub) + ndm
+    sums = torch.empty((ncand, rows, int(ntime)), dtype=torch.int32, device=chan_major.device)
+    hits = torch.empty_like(sums)
+    if ncand:
+        cutter.cut_offsets(ds.numpy(), dmt.numpy(), t0, fs, sums.data_ptr(), hits.data_ptr())
+    ns = int(nsub)
+    return (sums[:, :ns].contiguous(), hits[:, :ns].contiguous(), sums[:, ns:].contiguous(),
+            hits[:, ns:].contiguous())
+
+
 # ------------------------------------------------------------ RFI excision --
 def _check_rows(t: torch.Tensor, name: str) -> Tuple[int, int]:
     _check(t, torch.int8, name)

@@ -255,6 +255,91 @@ def cube_mean(cand: Dict) -> np.ndarray:
     return out
 
 
+# --------------------------------------------------------- burst cutouts ----
+BURST_MAGIC = b"PSBRST01"
+_BURST_HEADER = struct.Struct("<8s6IQ3d")  # magic, ncand ntime nsub ndm nchans nbits, nsamps, tsamp fch1 foff
+_BURST_CAND = struct.Struct("<QIIqff")     # sample, width, tscrunch, t0, dm, snr
+BURST_HEADER_FIELDS = ("ncand", "ntime", "nsub", "ndm", "nchans", "nbits", "nsamps", "tsamp", "fch1", "foff")
+_BURST_PLANES = ("ds_sums", "ds_hits", "dmt_sums", "dmt_hits")
+
+
+def write_burst_file(path: str, header: Dict, cands: List[Dict]) -> None:
+    """Writes a burst-cutout file byte for byte as the native
+    ``write_burst_file`` (csrc/src/burstcube.cpp): little-endian header
+    ``PSBRST01``, uint32 ncand ntime nsub ndm nchans nbits, uint64 nsamps,
+    double tsamp fch1 foff; per candidate uint64 sample, uint32 width, uint32
+    tscrunch, int64 t0, float dm, float snr, float dms[ndm], int32
+    nactive[nsub], then int32 ds_sums[nsub][ntime], ds_hits, dmt_sums[ndm][ntime],
+    dmt_hits.  ``header`` needs every field but ncand; each of ``cands`` is a
+    dict of those fields (snr optional).  Written to a temporary file, then renamed."""
+    import os
+
+    nt, ns, nd = int(header["ntime"]), int(header["nsub"]), int(header["ndm"])
+    blob = [_BURST_HEADER.pack(BURST_MAGIC, len(cands), nt, ns, nd, int(header["nchans"]), int(header["nbits"]),
+                               int(header["nsamps"]), float(header["tsamp"]), float(header["fch1"]),
+                               float(header["foff"]))]
+    shapes = {"ds_sums": (ns, nt), "ds_hits": (ns, nt), "dmt_sums": (nd, nt), "dmt_hits": (nd, nt)}
+    for i, c in enumerate(cands):
+        dms = np.ascontiguousarray(c["dms"], dtype="<f4")
+        na = np.ascontiguousarray(c["nactive"], dtype="<i4")
+        planes = [np.ascontiguousarray(c[k], dtype="<i4") for k in _BURST_PLANES]
+        if dms.shape != (nd,) or na.shape != (ns,) or any(p.shape != shapes[k] for p, k in zip(planes, _BURST_PLANES)):
+            raise ValueError(f"burst file: candidate {i} has the wrong shape")
+        blob += [_BURST_CAND.pack(int(c["sample"]), int(c["width"]), int(c["tscrunch"]), int(c["t0"]),
+                                  float(c["dm"]), float(c.get("snr", 0.0))), dms.tobytes(), na.tobytes()]
+        blob += [p.tobytes() for p in planes]
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class BurstCubeFile:
+    """Reader of a burst-cutout file (``bin/burstcube`` / ``python -m
+    peasoup_amd burst``): ``len``, ``header``, ``candidate(i)``."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._buf = open(path, "rb").read()
+        if len(self._buf) < _BURST_HEADER.size or self._buf[:8] != BURST_MAGIC:
+            raise ValueError(f"{path}: not a burst-cutout file")
+        vals = _BURST_HEADER.unpack_from(self._buf, 0)[1:]
+        self.header: Dict = dict(zip(BURST_HEADER_FIELDS, vals))
+        nt, ns, nd = self.header["ntime"], self.header["nsub"], self.header["ndm"]
+        self._rec = _BURST_CAND.size + 4 * nd + 4 * ns + 8 * (ns + nd) * nt
+        if len(self._buf) != _BURST_HEADER.size + self.header["ncand"] * self._rec:
+            raise ValueError(f"{path}: truncated burst-cutout file")
+
+    def __len__(self) -> int:
+        return int(self.header["ncand"])
+
+    def candidate(self, i: int) -> Dict:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        nt, ns, nd = self.header["ntime"], self.header["nsub"], self.header["ndm"]
+        o = _BURST_HEADER.size + i * self._rec
+        sample, width, f, t0, dm, snr = _BURST_CAND.unpack_from(self._buf, o)
+        o += _BURST_CAND.size
+        out = {"sample": sample, "width": width, "tscrunch": f, "t0": t0, "dm": dm, "snr": snr}
+        out["dms"] = np.frombuffer(self._buf, "<f4", nd, o).copy()
+        o += 4 * nd
+        out["nactive"] = np.frombuffer(self._buf, "<i4", ns, o).copy()
+        o += 4 * ns
+        for k, rows in zip(_BURST_PLANES, (ns, ns, nd, nd)):
+            out[k] = np.frombuffer(self._buf, "<i4", rows * nt, o).reshape(rows, nt).copy()
+            o += 4 * rows * nt
+        return out
+
+
+def burst_mean(sums, hits) -> np.ndarray:
+    """Mean raw sample of a cutout plane: sums / hits in float64, NaN where hits == 0."""
+    s = np.asarray(sums, dtype=np.float64)
+    h = np.asarray(hits, dtype=np.float64)
+    out = np.full(s.shape, np.nan, dtype=np.float64)
+    np.divide(s, h, out=out, where=h != 0)
+    return out
+
+
 # ---------------------------------------------------------------- RFI mask --
 RFI_MASK_MAGIC = b"PSMASK01"
 _MASK_HEADER = struct.Struct("<8s4I2Q4d")  # magic, nchans nblk nbits zero_dm, nsamps block, tsamp thresh chan_frac block_frac

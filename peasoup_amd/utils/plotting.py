@@ -93,6 +93,51 @@ def time_phase_panel(cand: Dict) -> np.ndarray:
     return out
 
 
+def burst_waterfall_panel(cand: Dict) -> np.ndarray:
+    """Dedispersed dynamic spectrum of a burst cutout (``BurstCubeFile.candidate``):
+    float64 [nsub, ntime], the mean raw sample with each subband's median over
+    its filled bins removed; bins without hits (and killed subbands) 0."""
+    from .outputs import burst_mean
+
+    m = burst_mean(cand["ds_sums"], cand["ds_hits"])
+    out = np.zeros(m.shape, dtype=np.float64)
+    for s in range(m.shape[0]):
+        filled = ~np.isnan(m[s])
+        if filled.any():
+            out[s, filled] = m[s, filled] - np.median(m[s, filled])
+    return out
+
+
+def burst_dmtime_panel(cand: Dict) -> np.ndarray:
+    """DM-time plane (the "bow tie") of a burst cutout: float64 [ndm, ntime],
+    the mean raw sample with each DM row's median over its filled bins
+    removed; bins without hits 0."""
+    from .outputs import burst_mean
+
+    m = burst_mean(cand["dmt_sums"], cand["dmt_hits"])
+    out = np.zeros(m.shape, dtype=np.float64)
+    for j in range(m.shape[0]):
+        filled = ~np.isnan(m[j])
+        if filled.any():
+            out[j, filled] = m[j, filled] - np.median(m[j, filled])
+    return out
+
+
+def burst_profile_panel(cand: Dict) -> np.ndarray:
+    """Band-summed profile of a burst cutout at the candidate's DM: float64
+    [ntime], the mean raw sample over the unkilled channels with the median
+    over the filled bins removed; bins without hits 0."""
+    from .outputs import burst_mean
+
+    m = burst_mean(np.asarray(cand["ds_sums"], dtype=np.int64).sum(axis=0),
+                   np.asarray(cand["ds_hits"], dtype=np.int64).sum(axis=0))
+    out = np.zeros(m.shape, dtype=np.float64)
+    filled = ~np.isnan(m)
+    if filled.any():
+        out[filled] = m[filled] - np.median(m[filled])
+    return out
+
+
 def _sizes(snr: np.ndarray) -> np.ndarray:
     s = np.asarray(snr, dtype=np.float64)
     if s.size == 0:

@@ -563,6 +563,80 @@ def fold_cube(values: np.ndarray, offsets: np.ndarray, period: float, af: float,
     return sums, hits.astype(np.int32), nactive
 
 
+# --------------------------------------------------------- burst cutouts ----
+# NumPy oracle of csrc/include/psoup/burstcube.hpp, written from its
+# definition in int64.
+def burst_tscrunch(width: int, tscrunch: int = 0) -> int:
+    return int(tscrunch) if tscrunch > 0 else max(1, int(width) // 2)
+
+
+def burst_t0(sample: int, width: int, f: int, ntime: int) -> int:
+    return int(sample) + int(width) // 2 - (int(ntime) // 2) * int(f)
+
+
+def burst_dms(dm: float, ndm: int, dm_half_range: float = 0.0) -> np.ndarray:
+    """float32 [ndm] DM rows of a candidate: row ndm // 2 is exactly ``dm``
+    (as float32), the rows step by 2 half / ndm and none is negative."""
+    d = float(np.float32(dm))
+    hr = float(np.float32(dm_half_range))
+    half = min(d, hr) if hr > 0 else d
+    step = 2.0 * half / ndm
+    j = np.arange(ndm, dtype=np.float64) - float(ndm // 2)
+    return np.maximum(0.0, d + j * step).astype(np.float32)
+
+
+def burst_rows(values: np.ndarray, chansets, offsets: np.ndarray, t0: int, f: int, ntime: int, nvalid: int = None):
+    """sums, hits (int64 [nrows, ntime]) of rows r with channels chansets[r]
+    and offsets[r] (int [nchans]): bin k sums values[u, c] over c in the set
+    and u = t0 + k f + i + offsets[r][c], i in [0, f), where 0 <= u < nvalid."""
+    n = values.shape[0] if nvalid is None else int(nvalid)
+    prefix = np.zeros((values.shape[1], n + 1), dtype=np.int64)
+    np.cumsum(values[:n].T.astype(np.int64), axis=1, out=prefix[:, 1:])
+    k = np.arange(ntime, dtype=np.int64)
+    nrows = len(chansets)
+    sums = np.zeros((nrows, ntime), dtype=np.int64)
+    hits = np.zeros((nrows, ntime), dtype=np.int64)
+    for r in range(nrows):
+        for c in chansets[r]:
+            lo = int(t0) + k * int(f) + int(offsets[r][c])
+            a, b = np.clip(lo, 0, n), np.clip(lo + int(f), 0, n)
+            sums[r] += prefix[c, b] - prefix[c, a]
+            hits[r] += b - a
+    return sums, hits
+
+
+def burst_cube_offsets(values: np.ndarray, ds_offsets: np.ndarray, dmt_offsets: np.ndarray, t0: int, f: int,
+                       ntime: int, nsub: int, killmask=None, nvalid: int = None) -> Dict:
+    """The cutout of one candidate at explicit offsets: ds_offsets int
+    [nchans], dmt_offsets int [ndm, nchans].  Returns a dict of ds_sums,
+    ds_hits (int32 [nsub, ntime]), dmt_sums, dmt_hits (int32 [ndm, ntime])
+    and nactive (int32 [nsub])."""
+    nchans = values.shape[1]
+    kill = np.ones(nchans, bool) if killmask is None else np.asarray(killmask) != 0
+    live = [int(c) for c in np.nonzero(kill)[0]]
+    subs = [[c for c in live if (c * nsub) // nchans == s] for s in range(nsub)]
+    ndm = len(dmt_offsets)
+    ds, dh = burst_rows(values, subs, [ds_offsets] * nsub, t0, f, ntime, nvalid)
+    ts, th = burst_rows(values, [live] * ndm, dmt_offsets, t0, f, ntime, nvalid)
+    assert max(ds.max(initial=0), ts.max(initial=0)) < 2 ** 31
+    return {"ds_sums": ds.astype(np.int32), "ds_hits": dh.astype(np.int32), "dmt_sums": ts.astype(np.int32),
+            "dmt_hits": th.astype(np.int32), "nactive": np.array([len(s) for s in subs], dtype=np.int32)}
+
+
+def burst_cube(values: np.ndarray, sample: int, width: int, dm: float, delays: np.ndarray, ntime: int, nsub: int,
+               ndm: int, tscrunch: int = 0, dm_half_range: float = 0.0, killmask=None, nvalid: int = None) -> Dict:
+    """The cutout of the candidate (sample, width, dm) of values [nsamps,
+    nchans] (raw samples): burst_cube_offsets' dict plus tscrunch (the f
+    used), t0 and dms (float32 [ndm])."""
+    f = burst_tscrunch(width, tscrunch)
+    t0 = burst_t0(sample, width, f, ntime)
+    dms = burst_dms(dm, ndm, dm_half_range)
+    out = burst_cube_offsets(values, dm_offsets([dm], delays)[0], dm_offsets(dms, delays), t0, f, ntime, nsub,
+                             killmask, nvalid)
+    out.update(tscrunch=f, t0=t0, dms=dms)
+    return out
+
+
 # ------------------------------------------------------------ RFI excision --
 # NumPy oracles of csrc/include/psoup/rfi.hpp, written from its definition in
 # int64 and float64.
