@@ -18,6 +18,7 @@
 
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <type_traits>
 #include <vector>
 #include <mutex>
@@ -1382,6 +1383,358 @@ harmonic_peaks_q8_kernel(const float* __restrict__ P, uint64_t pstride, const ui
   }
 }
 
+// Two-level screen (harmonic_set_flags bit 18).  On noise no bin passes the
+// per-bin screen above, and learning that bin by bin is the kernel's cost; a
+// bound over 8 neighbouring bins answers for all of them at once.
+//
+// Groups: the tile starts at the 16-byte boundary (in the shifted coordinate
+// bin + qshift) at or below `lo`, so its groups of 8 bins [b0 + 8 G, + 8) are
+// the 8-byte blocks of the fundamentals.  Alongside every staged 16-byte
+// chunk the tile keeps the maximum byte of each of its two aligned 8-byte
+// blocks: cmx[x >> 3] = max lds[x & ~7 .. (x & ~7) + 7].
+//
+// Window cover: term (h, m) of bin i reads idx(i) = (i m + 2^(h-1)) >> h
+// (idx(i) = i for the fundamental), which is monotone in i, so over the
+// group's bins f .. f + 7 every read lies in [idx(f), idx(f + 7)]; both ends
+// are computed with that expression, not approximated.  m < 2^h gives
+// idx(f + 7) - idx(f) <= 7: the window spans at most two aligned 8-byte
+// blocks, those of its two ends.
+// max >= element: u = max(cmx[block of idx(f)], cmx[block of idx(f + 7)])
+// is therefore at least every byte that term contributes for any bin of the
+// group, and the sum of the u of levels 0 .. h at least every bin's s_h.  So
+// if that sum stays at or below the same lim[h] for every h, and no u is 254
+// or more, the per-bin screen passes no bin of the group and none of its
+// terms is out of the byte range: the group is done.  No new constant enters,
+// only lim[] (argued above HarmTileQ).  Bytes staged from beyond `last`
+// repeat byte `last` or are row padding; they only widen a window that
+// already covers every read of the searched bins (idx(i) <= i <= last).
+//
+// Flagged groups (fewer than 1 in 1000 on noise) take today's per-bin screen
+// and exact sums, 8 groups = 64 consecutive-by-group bins per round over the
+// lanes of the wave that owns them: a wave owns a contiguous run of groups,
+// so a round's records are one idx-ascending chunk per level and the chunks
+// of a segment stay disjoint in idx (peakcluster.hip), and a peak-heavy tile
+// keeps all 64 lanes on flagged bins.
+template <int NLEV, int BPT>
+struct HarmTileG {
+  static constexpr int B = 256 * BPT;
+  static constexpr int NREG = 1 << NLEV;  // region 0: the fundamentals
+  static constexpr int mend(int h) { return h == 0 ? 2 : 1 << h; }        // odd m < mend(h)
+  static constexpr int half(int h) { return h == 0 ? 0 : 1 << (h - 1); }  // idx(i) = (i m + half) >> h
+  static constexpr int maxlen(int h, int m) { return (((B - 1) * m) >> h) + 2; }
+  // the fundamentals start on a chunk boundary; the gather ranges up to 15 bytes below their first bin
+  static constexpr int chunks(int h, int m) { return h == 0 ? B / 16 : (maxlen(h, m) + 30) / 16; }
+  static constexpr int region(int h, int m) { return h == 0 ? 0 : (1 << (h - 1)) + (m - 1) / 2; }
+  static constexpr int offset(int r) {  // bytes, a multiple of 16
+    int off = 0;
+    for (int h = 0; h <= NLEV; ++h)
+      for (int m = 1; m < mend(h); m += 2) {
+        if (region(h, m) == r) return off;
+        off += 16 * chunks(h, m);
+      }
+    return off;
+  }
+  static constexpr int TOTAL = offset(NREG);
+  static constexpr int iters() {
+    int n = 0;
+    for (int h = 0; h <= NLEV; ++h)
+      for (int m = 1; m < mend(h); m += 2) n += (chunks(h, m) + 255) / 256;
+    return n;
+  }
+  static constexpr int ITERS = iters();
+  static constexpr int GW = B / 32;              // groups per wave (4 waves, 8 bins per group)
+  static constexpr int GP = (GW + 63) / 64;      // groups per lane
+};
+
+typedef unsigned short us2_h __attribute__((ext_vector_type(2)));
+
+// Maximum byte of each 8-byte half of a chunk: {max of c.x, c.y bytes} |
+// {max of c.z, c.w bytes} << 8.  Packed 16-bit maxima order by the high byte
+// first, so a lane's high byte is the maximum of the operands' high bytes
+// whatever the low bytes hold.
+__device__ __forceinline__ uint32_t block_max2(uint4 c) {
+  auto pk = [](uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t,
+                              __builtin_elementwise_max(__builtin_bit_cast(us2_h, a), __builtin_bit_cast(us2_h, b)));
+  };
+  auto m8 = [&](uint32_t x, uint32_t y) {
+    const uint32_t px = pk(x, x << 8), py = pk(y, y << 8);  // bytes 1, 3: max(b1, b0), max(b3, b2)
+    const uint32_t m = pk(px, py);
+    return pk(m, m << 16) >> 24;  // byte 3: max(byte 3, byte 1)
+  };
+  return m8(c.x, c.y) | (m8(c.z, c.w) << 8);
+}
+
+#ifdef PSOUP_HARM_GROUP_STATS
+__device__ unsigned long long g_harm_group_stats[2];  // groups screened, groups flagged
+#endif
+
+template <int NLEV, int BPT, int SRC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7)))
+harmonic_peaks_q8g_kernel(const float* __restrict__ P, uint64_t pstride, const uint8_t* __restrict__ Q,
+                          uint64_t qstride, int lo, int hi, HarmParams hp, PeakRecord* __restrict__ out,
+                          uint32_t* __restrict__ count, int ntiles, int xcd_trials, HarmLim lim, HarmFromX fx) {
+  using Tl = HarmTileG<NLEV, BPT>;
+  constexpr int B = Tl::B;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[Tl::TOTAL];
+  __shared__ __attribute__((aligned(16))) uint8_t cmx[Tl::TOTAL / 8];
+  const uint32_t bid = blockIdx.x;
+  int k, tile;
+  if (xcd_trials & 1) {
+    const uint32_t slot = bid >> 3;
+    k = static_cast<int>((slot / ntiles) * 8 + (bid & 7u));
+    tile = static_cast<int>(slot % ntiles);
+  } else {
+    k = static_cast<int>(bid / ntiles);
+    tile = static_cast<int>(bid % ntiles);
+  }
+  constexpr bool FROMX = SRC == 1;
+  const float* p = FROMX ? nullptr : P + static_cast<uint64_t>(k) * pstride;
+  const int qs = fx.qshift;
+  const uint8_t* q = Q + static_cast<uint64_t>(k) * qstride + qs;  // q[b]: bin b
+  const int t = threadIdx.x;
+  const int b0 = ((lo + qs) & ~15) - qs + tile * B;  // >= -qs; bins below lo are never searched
+  const int last = hi - 1;
+  // first staged byte of range (h, m) in the shifted coordinate (a multiple of 16, >= 0)
+  auto r0s = [&](int h, int m) { return (((b0 * m + Tl::half(h)) >> h) + qs) & ~15; };
+  // ---- staging: the raw bytes as in harmonic_peaks_q8_kernel (the
+  // fundamentals as one more range), and each chunk's two block maxima
+  const bool interior = b0 + B <= hi;
+  uint4 tmp[Tl::ITERS];
+  if (interior) {
+    const uint32_t vo = 16u * static_cast<uint32_t>(t);
+    int it = 0;
+#pragma unroll
+    for (int h = 0; h <= NLEV; ++h) {
+#pragma unroll
+      for (int m = 1; m < Tl::mend(h); m += 2) {
+        const int r0 = r0s(h, m);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint8_t*>(q - qs + r0), 0, static_cast<int>(qstride) - r0, 0x00020000);
+#pragma unroll
+        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
+          if (t + 256 * e < Tl::chunks(h, m))
+            tmp[it] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 4096u * e, 0, 0));
+      }
+    }
+  } else {
+    int it = 0;
+#pragma unroll
+    for (int h = 0; h <= NLEV; ++h) {
+#pragma unroll
+      for (int m = 1; m < Tl::mend(h); m += 2) {
+        const int r0 = r0s(h, m) - qs;
+#pragma unroll
+        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
+          tmp[it] = load_q16(q, r0 + 16 * (t + 256 * e), last);
+      }
+    }
+  }
+  {
+    int it = 0;
+#pragma unroll
+    for (int h = 0; h <= NLEV; ++h) {
+#pragma unroll
+      for (int m = 1; m < Tl::mend(h); m += 2) {
+        uint4* dst = reinterpret_cast<uint4*>(lds + Tl::offset(Tl::region(h, m)));
+        uint16_t* dmx = reinterpret_cast<uint16_t*>(cmx + Tl::offset(Tl::region(h, m)) / 8);
+#pragma unroll
+        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
+          if (t + 256 * e < Tl::chunks(h, m)) {
+            dst[t + 256 * e] = tmp[it];
+            dmx[t + 256 * e] = static_cast<uint16_t>(block_max2(tmp[it]));
+          }
+      }
+    }
+  }
+  __syncthreads();
+  // ---- coarse pass: lane l of wave w takes groups w GW + l + 64 g.  Block of
+  // the byte of idx: (offset - r0s) / 8 + ((idx + qs) >> 3), and idx + qs =
+  // (i m + half + (qs << h)) >> h; 64 groups on add m << (6 - h) blocks exactly.
+  const int lane = t & 63, w = t >> 6;
+  const int gl = Tl::GW < 64 ? min(lane, Tl::GW - 1) : lane;  // (lanes past the wave's groups repeat its last)
+  const int G = w * Tl::GW + gl;
+  int sb[Tl::GP], mxs[Tl::GP];
+  bool flag[Tl::GP];
+#pragma unroll
+  for (int g = 0; g < Tl::GP; ++g) {
+    sb[g] = 0;
+    mxs[g] = 0;
+    flag[g] = false;
+  }
+#pragma unroll
+  for (int h = 0; h <= NLEV; ++h) {
+#pragma unroll
+    for (int m = 1; m < Tl::mend(h); m += 2) {
+      const int sp = b0 * m + Tl::half(h) + (qs << h);              // block-uniform, >= 0
+      const int cb = Tl::offset(Tl::region(h, m)) / 8 - (r0s(h, m) >> 3);
+      const int a = ((sp + 8 * m * G) >> (h + 3)) + cb;             // block of idx(f)
+      const int b = ((sp + 7 * m + 8 * m * G) >> (h + 3)) + cb;     // block of idx(f + 7)
+#pragma unroll
+      for (int g = 0; g < Tl::GP; ++g) {
+        const int v = max(static_cast<int>(cmx[a + g * (m << (6 - h))]), static_cast<int>(cmx[b + g * (m << (6 - h))]));
+        sb[g] += v;
+        mxs[g] = max(mxs[g], v);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < Tl::GP; ++g) flag[g] = flag[g] | (sb[g] > lim.v[h]);
+  }
+  unsigned long long fm[Tl::GP];
+  bool none = true;
+#pragma unroll
+  for (int g = 0; g < Tl::GP; ++g) {
+    const bool f = (flag[g] | (mxs[g] >= 254)) & (lane + 64 * g < Tl::GW);
+    fm[g] = __ballot(f);
+    none = none & (fm[g] == 0ull);
+  }
+#ifdef PSOUP_HARM_GROUP_STATS
+  if (lane == 0) {
+    unsigned long long nf = 0;
+#pragma unroll
+    for (int g = 0; g < Tl::GP; ++g) nf += __popcll(fm[g]);
+    atomicAdd(&g_harm_group_stats[0], static_cast<unsigned long long>(Tl::GW));
+    atomicAdd(&g_harm_group_stats[1], nf);
+  }
+#endif
+  if (none) return;  // the noise case: no group of this wave can hold a candidate
+  // ---- flagged groups: the per-bin screen and the exact sums
+  const float thr = hp.thresh;
+  const uint32_t seg0 = (static_cast<uint32_t>(k) + hp.trial_base) * 8u;
+  bool inner = true;  // block-uniform: the whole tile lies inside every level's search range
+#pragma unroll
+  for (int h = 0; h <= NLEV; ++h) inner = inner & (b0 >= hp.start[h]) & (b0 + B <= hp.end[h]);
+  const float2* z = nullptr;
+  float mean = 0.f, sigma = 1.f, rsig = 1.f;
+  uint32_t M = 0;
+  if constexpr (FROMX) {
+    z = fx.X + static_cast<uint64_t>(k) * fx.xstride;
+    const float* st = fx.tsrc ? fx.stats + 4 * fx.tsrc[k] : fx.stats;
+    mean = st[0] * fx.nscale;
+    sigma = st[2] * fx.nscale;
+    rsig = 1.0f / sigma;  // as the r2c kernel
+    M = fx.n1 << fx.log2_n2;
+  }
+  auto pv = [&](int b) -> float {
+    if constexpr (FROMX) {
+      const uint32_t ub = static_cast<uint32_t>(b);
+      const float2 x0 = x_canon(z, ub, M, fx.log2_n2, fx.n1, fx.rt);
+      const float2 xl = ub > 0 ? x_canon(z, ub - 1, M, fx.log2_n2, fx.n1, fx.rt) : make_float2(0.f, 0.f);
+      return dev::div_rn(dev::interbin(x0, xl) - mean, sigma, rsig);
+    } else if constexpr (SRC == 2) {
+      return p[spec_pblk_index(static_cast<uint32_t>(b), fx.log2_n2, fx.n1)];
+    } else {
+      return p[b];
+    }
+  };
+  // the screening byte of term (h, m) of bin i (any bin of the tile)
+  auto qb = [&](int h, int m, int i) -> int {
+    return lds[Tl::offset(Tl::region(h, m)) + (((i * m + Tl::half(h) + (qs << h)) >> h) - r0s(h, m))];
+  };
+  // the per-bin screen of harmonic_peaks_q8_kernel
+  auto fine = [&](int i) -> bool {
+    int sq = qb(0, 1, i), mx = sq;
+    bool cand = sq > lim.v[0];
+#pragma unroll
+    for (int h = 1; h <= NLEV; ++h) {
+#pragma unroll
+      for (int m = 1; m < (1 << h); m += 2) {
+        const int v = qb(h, m, i);
+        sq += v;
+        mx = max(mx, v);
+      }
+      cand = cand | (sq > lim.v[h]);
+    }
+    return cand | (mx >= 254);
+  };
+  // one round: up to 8 flagged groups of `mask` (groups gbase + bit), 8 lanes each
+  auto round = [&](int gbase, unsigned long long& mask) {
+    int mine = -1;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int pos = mask ? __builtin_ctzll(mask) : -1;  // wave-uniform
+      mask &= mask - 1ull;
+      mine = (lane >> 3) == r ? pos : mine;
+    }
+    const int i = b0 + 8 * (gbase + max(mine, 0)) + (lane & 7);
+    bool cand = (mine >= 0) & (i >= lo) & (i < hi);  // the tile's bins outside [lo, hi) are not searched
+    cand = cand & fine(i);
+    if (__ballot(cand) == 0ull) return;
+    bool pred[NLEV + 1];
+    float o[NLEV + 1];
+#pragma unroll
+    for (int h = 0; h <= NLEV; ++h) {
+      pred[h] = false;
+      o[h] = 0.f;
+    }
+    if (cand) {
+      // the fp32 sums in the reference order (harmonic_peaks_kernel)
+      float val = pv(i);
+      float sum[NLEV + 1];
+      sum[0] = val;
+      if constexpr (NLEV >= 1) {
+        val += pv((i + 1) >> 1);
+        sum[1] = val;
+      }
+      if constexpr (NLEV >= 2) {
+        val += pv((i * 3 + 2) >> 2);  // reference order: 3/4 before 1/4
+        val += pv((i + 2) >> 2);
+        sum[2] = val;
+      }
+      // (levels 3+ in runtime loops when the bins are recomputed, as in
+      // harmonic_peaks_q8_kernel)
+      if constexpr (NLEV >= 3) {
+        if constexpr (FROMX) {
+#pragma unroll 1
+          for (int m = 1; m < 8; m += 2) val += pv((i * m + 4) >> 3);
+        } else {
+#pragma unroll
+          for (int m = 1; m < 8; m += 2) val += pv((i * m + 4) >> 3);
+        }
+        sum[3] = val;
+      }
+      if constexpr (NLEV >= 4) {
+        if constexpr (FROMX) {
+#pragma unroll 1
+          for (int m = 1; m < 16; m += 2) val += pv((i * m + 8) >> 4);
+        } else {
+#pragma unroll
+          for (int m = 1; m < 16; m += 2) val += pv((i * m + 8) >> 4);
+        }
+        sum[4] = val;
+      }
+      if constexpr (NLEV >= 5) {
+        if constexpr (FROMX) {
+#pragma unroll 1
+          for (int m = 1; m < 32; m += 2) val += pv((i * m + 16) >> 5);
+        } else {
+#pragma unroll
+          for (int m = 1; m < 32; m += 2) val += pv((i * m + 16) >> 5);
+        }
+        sum[5] = val;
+      }
+#pragma unroll
+      for (int h = 0; h <= NLEV; ++h) {
+        if (h == 2)
+          o[h] = sum[h] * 0.5f;
+        else if (h == 4)
+          o[h] = sum[h] * 0.25f;
+        else
+          o[h] = h == 0 ? sum[0] : static_cast<float>(static_cast<double>(sum[h]) * c_level_scale[h]);
+        const bool in_range = inner | ((i >= hp.start[h]) & (i < hp.end[h]));
+        pred[h] = in_range & (o[h] > thr);
+      }
+    }
+    emit_levels<NLEV + 1>(pred, 0, NLEV, seg0, i, o, out, count, hp);
+  };
+#pragma unroll
+  for (int g = 0; g < Tl::GP; ++g) {
+    unsigned long long mask = fm[g];
+#pragma unroll 1
+    while (mask != 0ull) round(w * Tl::GW + 64 * g, mask);
+  }
+}
+
 __global__ void __launch_bounds__(256) quantize_q8_kernel(const float* __restrict__ P, uint64_t pstride, uint64_t n,
                                                           uint8_t* __restrict__ Q, uint64_t qstride) {
   const float* p = P + blockIdx.y * pstride;
@@ -1480,9 +1833,11 @@ namespace {
 // bits 8-15: dynamic-LDS occupancy cap in KiB of the two-phase kernel;
 // bit 16: the screened kernel up to 3 levels with 16 bins per thread (a
 // 4096-bin tile: twice the staging per workgroup in flight; bench +2.7% over
-// 8); bit 17: 32 bins per thread.
+// 8); bit 17: 32 bins per thread; bit 18: the screened kernel screens groups
+// of 8 bins on block maxima before any single bin (harmonic_peaks_q8g_kernel;
+// cleared: harmonic_peaks_q8_kernel, the per-bin screen alone).
 // Engines read bits 2, 3 and 6 when they are built.
-int g_harm_flags = 1 | 8 | 32 | 64 | (10 << 8) | 65536;
+int g_harm_flags = 1 | 8 | 32 | 64 | (10 << 8) | 65536 | 262144;
 
 // Mixed-radix n = m p (p a power of two, m odd): gather of the m strided
 // columns, and the length-m combination with the twiddles W_n^(n1 k)
@@ -1794,6 +2149,23 @@ void harmonic_peaks_batch(const float* P, uint64_t nbins, uint64_t pstride, int 
     }
     auto oneq_bp = [&](auto nl_c, auto bp_c) {
       constexpr int NL = decltype(nl_c)::value, BP = decltype(bp_c)::value;
+      if (g_harm_flags & 262144) {
+        // two-level screen: tiles from the 16-byte boundary of the shifted row at or below lo
+        const int lo16 = ((lo + fxv.qshift) & ~15) - fxv.qshift;
+        const int nt = (hi - lo16 + HarmTileG<NL, BP>::B - 1) / HarmTileG<NL, BP>::B;
+        PSOUP_CHECK(static_cast<int64_t>(nt) * K < (int64_t(1) << 31), "harmonic grid too large");
+        const dim3 grid(static_cast<unsigned>(nt * K));
+        if (src == 1)
+          harmonic_peaks_q8g_kernel<NL, BP, 1><<<grid, 256, 0, s>>>(P, pstride, Q, qstride, lo, hi, hp, out, count, nt,
+                                                                    xcd, lim, fxv);
+        else if (src == 2)
+          harmonic_peaks_q8g_kernel<NL, BP, 2><<<grid, 256, 0, s>>>(P, pstride, Q, qstride, lo, hi, hp, out, count, nt,
+                                                                    xcd, lim, fxv);
+        else
+          harmonic_peaks_q8g_kernel<NL, BP, 0><<<grid, 256, 0, s>>>(P, pstride, Q, qstride, lo, hi, hp, out, count, nt,
+                                                                    xcd, lim, fxv);
+        return;
+      }
       const int nt = ntiles_of(HarmTileQ<NL, BP>::B);
       PSOUP_CHECK(static_cast<int64_t>(nt) * K < (int64_t(1) << 31), "harmonic grid too large");
       const dim3 grid(static_cast<unsigned>(nt * K));
@@ -1830,6 +2202,16 @@ void harmonic_peaks_batch(const float* P, uint64_t nbins, uint64_t pstride, int 
       default: oneq(std::integral_constant<int, 5>{}); break;
     }
     post_launch_check("harmonic_peaks_q8_kernel", s);
+#ifdef PSOUP_HARM_GROUP_STATS
+    {  // debug build only: share of groups the coarse screen flags (synchronises)
+      unsigned long long st[2];
+      PSOUP_HIP_CHECK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_harm_group_stats), sizeof(st)));
+      static int calls = 0;
+      if ((++calls & 3) == 0)
+        fprintf(stderr, "harm groups: %llu screened, %llu flagged (%.3g)\n", st[0], st[1],
+                st[0] ? static_cast<double>(st[1]) / static_cast<double>(st[0]) : 0.0);
+    }
+#endif
     return;
   }
   auto one = [&](auto nl_c, auto bp_c) {
