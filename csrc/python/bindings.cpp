@@ -123,6 +123,7 @@ void bind_sp(py::module_& m);   // bind_sp.cpp
 void bind_cube(py::module_& m);  // bind_cube.cpp
 void bind_rfi(py::module_& m);   // bind_rfi.cpp
 void bind_burst(py::module_& m); // bind_burst.cpp
+void bind_opt(py::module_& m);   // bind_opt.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -697,6 +698,7 @@ PYBIND11_MODULE(_C, m) {
   bind_cube(m);
   bind_rfi(m);
   bind_burst(m);
+  bind_opt(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -25,16 +25,7 @@ int64_t burst_t0(uint64_t sample, uint32_t width, int f, int ntime) {
   return tc - static_cast<int64_t>(ntime / 2) * f;
 }
 
-std::vector<float> burst_dms(float dm, int ndm, float dm_half_range) {
-  PSOUP_CHECK(ndm >= 1, "burst cube: ndm must be at least 1");
-  const double d = static_cast<double>(dm);
-  const double half = dm_half_range > 0 ? std::min(d, static_cast<double>(dm_half_range)) : d;
-  const double step = 2.0 * half / ndm;
-  std::vector<float> out(static_cast<size_t>(ndm));
-  for (int j = 0; j < ndm; ++j)
-    out[static_cast<size_t>(j)] = static_cast<float>(std::max(0.0, d + static_cast<double>(j - ndm / 2) * step));
-  return out;
-}
+// burst_dms: burst_dms.cpp (host only; cubeopt shares it)
 
 // ----------------------------------------------------------- candidates ----
 namespace {

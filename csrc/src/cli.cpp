@@ -1,5 +1,6 @@
 #include "psoup/cli.hpp"
 #include "psoup/burstcube.hpp"
+#include "psoup/cubeopt.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
 #include "psoup/singlepulse.hpp"
@@ -495,6 +496,53 @@ bool parse_burst_cmdline(BurstCubeCmdLineOptions& a, const std::vector<std::stri
   }
   if (!(a.dm_half_range >= 0) || a.limit < 0) {
     std::cerr << "Error: --dm_half_range and --limit must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_opt_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_cubeopt.opt", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_opt_cmdline(CubeOptCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_opt_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "Fold cubes to search (a foldcube output)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_n("", "ndm", "DM trials (1..256); row ndm / 2 is the candidate's DM", a.ndm),
+      val_n("", "dm_half_range", "DM trials span the candidate's DM -/+ this (0 = the DM itself: 0..2 DM)",
+            a.dm_half_range),
+      val_n("", "np", "Period trials (odd, 1..257)", a.np),
+      val_n("", "p_step", "Period step: bins of drift across the fold", a.p_step),
+      val_n("", "npd", "Acceleration trials (odd, 1..129)", a.npd),
+      val_n("", "pd_step", "Acceleration step: bins of curvature at the middle of the fold", a.pd_step),
+      val_n("", "limit", "At most this many candidates from the top of the file", a.limit),
+      sw("v", "verbose", "verbose mode: one line per candidate", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup cube-optimiser extension - DM, period and acceleration search on fold cubes",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.ndm < 1 || a.ndm > 256) {
+    std::cerr << "Error: --ndm must be in 1..256" << std::endl;
+    return false;
+  }
+  if (a.np < 1 || a.np > 257 || a.np % 2 == 0) {
+    std::cerr << "Error: --np must be odd and in 1..257" << std::endl;
+    return false;
+  }
+  if (a.npd < 1 || a.npd > 129 || a.npd % 2 == 0) {
+    std::cerr << "Error: --npd must be odd and in 1..129" << std::endl;
+    return false;
+  }
+  if (!(a.p_step >= 0) || !(a.pd_step >= 0) || !(a.dm_half_range >= 0) || a.limit < 0 || !(a.p_step < 1e6) ||
+      !(a.pd_step < 1e6) || !(a.dm_half_range < 1e9f)) {
+    std::cerr << "Error: --p_step, --pd_step, --dm_half_range and --limit must be finite and non-negative"
+              << std::endl;
     return false;
   }
   return true;

@@ -3,7 +3,8 @@
 flags]`` for the single-pulse search, ``python -m peasoup_amd cube [foldcube
 flags]`` for the filterbank fold cubes of candidates, ``python -m peasoup_amd
 burst [burstcube flags]`` for the cutouts of single-pulse candidates, ``python
--m peasoup_amd clean [rficlean flags]`` for the RFI excision) -- the peasoup CLI as a
+-m peasoup_amd opt [cubeopt flags]`` for the DM / period / acceleration search
+on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -73,6 +74,8 @@ def main(argv=None) -> int:
         return _main_cube(["foldcube"] + argv[2:])
     if len(argv) > 1 and argv[1] == "burst":
         return _main_burst(["burstcube"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "opt":
+        return _main_opt(["cubeopt"] + argv[2:])
     if len(argv) > 1 and argv[1] == "clean":
         return _main_clean(["rficlean"] + argv[2:])
     argv[0] = "peasoup"
@@ -172,6 +175,26 @@ def _main_burst(argv) -> int:
         _fail_hard("burst", e)
     if run is not None and args.verbose:
         print(f"Wrote {run.ncand} burst cutouts to {args.outfilename}")
+    return 0
+
+
+def _main_opt(argv) -> int:
+    from . import _C
+    from .models.cubeopt import print_records, run_cube_opt
+
+    ok, exit_now, args = _C.parse_opt_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        run = run_cube_opt(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("opt", e)
+    if run is not None and args.verbose:
+        print_records(run)
+        print(f"Wrote {run.ncand} cubeopt records to {args.outfilename}")
     return 0
 
 

@@ -28,9 +28,11 @@ def _jobs() -> int:
     return max(1, min(16, os.cpu_count() or 4))
 
 
-def build(verbose: bool = False, clean: bool = False, sanitize: str = "") -> None:
+def build(verbose: bool = False, clean: bool = False, sanitize: str = "",
+          sanitize_target: str = "psoup_unit_tests") -> None:
     """Configure (once) and build every native target for gfx950 (or, with
-    ``sanitize``, only the host unit tests under that host sanitizer)."""
+    ``sanitize``, only the host unit tests ``sanitize_target`` under that host
+    sanitizer)."""
     build_dir = BUILD_DIR if not sanitize else REPO / f"build-{sanitize}"
     if clean and build_dir.exists():
         shutil.rmtree(build_dir)
@@ -50,7 +52,7 @@ def build(verbose: bool = False, clean: bool = False, sanitize: str = "") -> Non
         subprocess.run(cmd, check=True, env=env, stdout=None if verbose else subprocess.DEVNULL)
     cmd = ["cmake", "--build", str(build_dir), "-j", str(_jobs())]
     if sanitize:
-        cmd += ["--target", "psoup_unit_tests"]
+        cmd += ["--target", sanitize_target]
     res = subprocess.run(cmd, env=env, capture_output=not verbose, text=True)
     if res.returncode != 0:
         out = (res.stdout or "") + (res.stderr or "")

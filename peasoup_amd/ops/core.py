@@ -586,6 +586,69 @@ def fold_cube(chan_major: torch.Tensor, offsets: torch.Tensor, periods, accels, 
     return sums, hits
 
 
+# ---------------------------------------------------------------- cubeopt --
+def cube_search(d: torch.Tensor, sdm: torch.Tensor, st: torch.Tensor):
+    """The search of cubeopt alone (csrc/include/psoup/cubeopt.hpp, step 3),
+    with explicit shift tables and a leading candidate axis: ``d`` int32
+    [ncand, nints, nsub, nbins], ``sdm`` int32 [ncand, ndm, nsub], ``st`` int32
+    [ncand, np, npd, nints], every shift in [0, nbins).  Returns (best_val
+    [ncand, nw], best_idx [ncand, nw], dmcurve [ncand, nw, ndm], ppd [ncand,
+    nw, np, npd], centre [ncand, nw]), int32 tensors on the current device;
+    exactly the NumPy oracle's (utils.reference.cube_opt_search).  Tensors
+    given on the host are uploaded; the kernels read and write device memory
+    through raw addresses and the results stay on the device.  The shift
+    tables are checked before anything is launched (the kernel indexes with
+    them): ``ValueError`` naming the candidate."""
+    for t, name in ((d, "d"), (sdm, "sdm"), (st, "st")):
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name} must be int32")
+    if d.dim() != 4 or sdm.dim() != 3 or st.dim() != 4:
+        raise ValueError("d [ncand, nints, nsub, nbins], sdm [ncand, ndm, nsub], st [ncand, np, npd, nints]")
+    ncand, nints, nsub, nbins = (int(x) for x in d.shape)
+    ndm, np_, npd = int(sdm.shape[1]), int(st.shape[1]), int(st.shape[2])
+    if tuple(sdm.shape) != (ncand, ndm, nsub) or tuple(st.shape) != (ncand, np_, npd, nints):
+        raise ValueError("sdm must be [ncand, ndm, nsub] and st [ncand, np, npd, nints] for d's ncand, nsub and nints")
+    if nints * nbins > 16384 or ndm * np_ * npd * nbins >= 2 ** 31:
+        raise ValueError("nints * nbins must be at most 16384 and ndm * np * npd * nbins below 2^31")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d, sdm, st = (t.detach().to(dev).contiguous() for t in (d, sdm, st))
+    for t, name in ((sdm, "DM"), (st, "subint")):
+        bad = ((t < 0) | (t >= nbins)).reshape(ncand, -1).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"cube search: candidate {int(torch.nonzero(bad)[0])} has a {name} shift outside [0, nbins)")
+    opt = _C.CubeOptimiser(_C.CubeOptGeom(nints, nsub, nbins), _C.CubeOptGrid(ndm, 0.0, np_, 1.0, npd, 1.0), _s())
+    nw = opt.nwidths
+    out = [torch.empty((ncand,) + shape, dtype=torch.int32, device=dev)
+           for shape in ((nw,), (nw,), (nw, ndm), (nw, np_, npd), (nw,))]
+    if ncand:
+        opt.search_device(d.data_ptr(), sdm.data_ptr(), st.data_ptr(), ncand, *(t.data_ptr() for t in out))
+    return tuple(out)
+
+
+def cube_optimise(candidates, header: Dict, ndm: int = 64, np_: int = 65, npd: int = 33, dm_half_range: float = 0.0,
+                  p_step: float = 1.0, pd_step: float = 1.0, delays=None, batch_bytes: int = None) -> List[Dict]:
+    """cubeopt on candidate dicts (period, dm, acc, nactive, hits, sums) of a
+    fold-cube file with ``header``: one record per candidate, exactly
+    utils.reference.cube_optimise's.  ``delays``: the float32 delay table
+    (default: the header's).  Every candidate is validated before anything is
+    launched."""
+    cands = list(candidates)
+    if not cands:
+        return []
+    nints, nsub, nbins = (int(x) for x in np.asarray(cands[0]["sums"]).shape)
+    geom = _C.CubeOptGeom(nints, nsub, nbins, int(header["nchans"]), int(header["fold_nsamps"]),
+                          float(header["tsamp"]), float(header["fch1"]), float(header["foff"]))
+    grid = _C.CubeOptGrid(int(ndm), float(dm_half_range), int(np_), float(p_step), int(npd), float(pd_step))
+    if delays is None:
+        delays = _C.generate_delay_table(geom.nchans, geom.tsamp, geom.fch1, geom.foff)
+    kw = {} if batch_bytes is None else {"batch_bytes": int(batch_bytes)}
+    opt = _C.CubeOptimiser(geom, grid, _s(), **kw)
+    recs = opt.optimise([dict(c) for c in cands], [float(x) for x in delays])
+    for r, c in zip(recs, cands):
+        r.update(period=float(c["period"]), dm=float(np.float32(c["dm"])), acc=float(np.float32(c["acc"])))
+    return recs
+
+
 # ----------------------------------------------------------- burst cutouts --
 def burst_cube(chan_major: torch.Tensor, ds_offsets: torch.Tensor, dmt_offsets: torch.Tensor, samples, tscrunch,
                ntime: int = 256, nsub: int = 256, bias: int = 0, killmask=None, nsamps: int = None,

@@ -255,6 +255,89 @@ def cube_mean(cand: Dict) -> np.ndarray:
     return out
 
 
+# --------------------------------------------------------------- cubeopt ----
+OPT_MAGIC = b"PSOPT001"
+_OPT_HEADER = struct.Struct("<8s10IQ6d")  # magic, ncand nints nsub nbins nchans ndm np npd nw 0, fold_nsamps, 6 doubles
+_OPT_CAND = struct.Struct("<dff5df7Iqd")  # period dm acc | snr snr_in snr_dm0 opt_period opt_acc | opt_dm | 7 u32 | mtot v
+OPT_HEADER_FIELDS = ("ncand", "nints", "nsub", "nbins", "nchans", "ndm", "np", "npd", "nw", "fold_nsamps", "tsamp",
+                     "fch1", "foff", "p_step", "pd_step", "dm_half_range")
+_OPT_SCALARS = ("period", "dm", "acc", "snr", "snr_in", "snr_dm0", "opt_period", "opt_acc", "opt_dm", "opt_width",
+                "opt_bin", "opt_kd", "opt_kp", "opt_kpd", "flags")
+
+
+def _opt_arrays(h: Dict):
+    nw, ndm, np_, npd, nb = (int(h[k]) for k in ("nw", "ndm", "np", "npd", "nbins"))
+    return (("dms", "<f4", (ndm,)), ("best_val", "<i4", (nw,)), ("best_idx", "<i4", (nw,)), ("centre", "<i4", (nw,)),
+            ("dmcurve", "<i4", (nw, ndm)), ("ppd", "<i4", (nw, np_, npd)), ("profile", "<i4", (nb,)))
+
+
+def write_opt_file(path: str, header: Dict, records: List[Dict]) -> None:
+    """Writes a cubeopt result file byte for byte as the native
+    ``write_opt_file`` (csrc/src/cubeopt.cpp): little-endian ``PSOPT001``,
+    uint32 ncand nints nsub nbins nchans ndm np npd nw and a zero, uint64
+    fold_nsamps, double tsamp fch1 foff p_step pd_step dm_half_range (104
+    bytes); per candidate double period, float dm, float acc, double snr
+    snr_in snr_dm0 opt_period opt_acc, float opt_dm, uint32 opt_width opt_bin
+    opt_kd opt_kp opt_kpd flags and a zero, int64 mtot, double v (104 bytes),
+    then float dms[ndm], int32 best_val[nw], best_idx[nw], centre[nw],
+    dmcurve[nw][ndm], ppd[nw][np][npd], profile[nbins].  ``header`` needs
+    every field but ncand.  Written to a temporary file, then renamed."""
+    import os
+
+    h = dict(header, ncand=len(records))
+    blob = [_OPT_HEADER.pack(OPT_MAGIC, *(int(h[k]) for k in OPT_HEADER_FIELDS[:9]), 0, int(h["fold_nsamps"]),
+                             *(float(h[k]) for k in OPT_HEADER_FIELDS[10:]))]
+    for i, r in enumerate(records):
+        blob.append(_OPT_CAND.pack(float(r["period"]), float(r["dm"]), float(r["acc"]), float(r["snr"]),
+                                   float(r["snr_in"]), float(r["snr_dm0"]), float(r["opt_period"]),
+                                   float(r["opt_acc"]), float(r["opt_dm"]), int(r["opt_width"]), int(r["opt_bin"]),
+                                   int(r["opt_kd"]), int(r["opt_kp"]), int(r["opt_kpd"]), int(r["flags"]), 0,
+                                   int(r["mtot"]), float(r["v"])))
+        for name, dt, shape in _opt_arrays(h):
+            a = np.ascontiguousarray(r[name], dtype=dt)
+            if a.shape != shape:
+                raise ValueError(f"opt file: candidate {i}: {name} has the wrong shape")
+            blob.append(a.tobytes())
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class FoldOptFile:
+    """Reader of a cubeopt result file (``bin/cubeopt`` / ``python -m
+    peasoup_amd opt``): ``len``, ``header``, ``candidate(i)``."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._buf = open(path, "rb").read()
+        if len(self._buf) < _OPT_HEADER.size or self._buf[:8] != OPT_MAGIC:
+            raise ValueError(f"{path}: not a cubeopt result file")
+        vals = _OPT_HEADER.unpack_from(self._buf, 0)[1:]
+        self.header: Dict = dict(zip(OPT_HEADER_FIELDS, vals[:9] + vals[10:]))
+        self._arrays = _opt_arrays(self.header)
+        self._rec = _OPT_CAND.size + sum(np.dtype(dt).itemsize * int(np.prod(sh)) for _, dt, sh in self._arrays)
+        if len(self._buf) != _OPT_HEADER.size + self.header["ncand"] * self._rec:
+            raise ValueError(f"{path}: truncated cubeopt result file")
+
+    def __len__(self) -> int:
+        return int(self.header["ncand"])
+
+    def candidate(self, i: int) -> Dict:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        o = _OPT_HEADER.size + i * self._rec
+        v = _OPT_CAND.unpack_from(self._buf, o)
+        out = dict(zip(_OPT_SCALARS, v[:15]))
+        out["mtot"], out["v"] = v[16], v[17]
+        o += _OPT_CAND.size
+        for name, dt, shape in self._arrays:
+            n = int(np.prod(shape))
+            out[name] = np.frombuffer(self._buf, dt, n, o).reshape(shape).copy()
+            o += n * np.dtype(dt).itemsize
+        return out
+
+
 # --------------------------------------------------------- burst cutouts ----
 BURST_MAGIC = b"PSBRST01"
 _BURST_HEADER = struct.Struct("<8s6IQ3d")  # magic, ncand ntime nsub ndm nchans nbits, nsamps, tsamp fch1 foff

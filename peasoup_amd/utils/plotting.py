@@ -138,6 +138,30 @@ def burst_profile_panel(cand: Dict) -> np.ndarray:
     return out
 
 
+def _opt_snr_plane(rec: Dict, vals: np.ndarray) -> np.ndarray:
+    """The S/N (cubeopt.hpp, step 4) of box sums ``vals`` [nw, ...], maximised over the widths."""
+    nbins = int(np.asarray(rec["profile"]).shape[0])
+    vals = np.asarray(vals, dtype=np.float64)
+    if not rec["v"] > 0:
+        return np.zeros(vals.shape[1:], dtype=np.float64)
+    w = (2.0 ** np.arange(vals.shape[0])).reshape((-1,) + (1,) * (vals.ndim - 1))
+    snr = (vals - w * float(rec["mtot"]) / nbins) / np.sqrt(float(rec["v"]) * w * (1.0 - w / nbins))
+    return snr.max(axis=0)
+
+
+def dm_curve_panel(rec: Dict) -> Tuple[np.ndarray, np.ndarray]:
+    """(dms float64 [ndm], S/N float64 [ndm]) of a cubeopt record: for every DM
+    trial the best S/N over the period and acceleration trials, bins and widths."""
+    return np.asarray(rec["dms"], dtype=np.float64), _opt_snr_plane(rec, rec["dmcurve"])
+
+
+def p_pdot_panel(rec: Dict) -> np.ndarray:
+    """float64 [npd, np] of a cubeopt record: for every (acceleration,
+    period) trial the best S/N over the DM trials, bins and widths; the
+    period trials run along x."""
+    return _opt_snr_plane(rec, rec["ppd"]).T.copy()
+
+
 def _sizes(snr: np.ndarray) -> np.ndarray:
     s = np.asarray(snr, dtype=np.float64)
     if s.size == 0:
@@ -152,10 +176,17 @@ class CandidatePlotter:
     ``.npz`` panels when matplotlib is missing) and returns its path."""
 
     def __init__(self, outdir: Optional[str] = None, overview: Optional[str] = None,
-                 candidates: Optional[str] = None, cubes: Optional[str] = None):
+                 candidates: Optional[str] = None, cubes: Optional[str] = None, opt: Optional[str] = None):
         # cubes: a fold-cube file whose candidate i belongs to candidate i of
         # the overview (python -m peasoup_amd cube --overview); adds the
         # frequency-phase and time-phase panels
+        # opt: the cubeopt result file of those cubes; adds the S/N-DM curve
+        # and the P-Pdot plane
+        self.opt = None
+        if opt:
+            from .outputs import FoldOptFile
+
+            self.opt = FoldOptFile(opt)
         self.cubes = None
         if cubes:
             from .outputs import FoldCubeFile
@@ -187,6 +218,10 @@ class CandidatePlotter:
             cube = self.cubes.candidate(idx)
             p["freq_phase"] = freq_phase_panel(cube)
             p["time_phase"] = time_phase_panel(cube)
+        if self.opt is not None and idx < len(self.opt):
+            rec = self.opt.candidate(idx)
+            p["opt_dms"], p["opt_dm_snr"] = dm_curve_panel(rec)
+            p["opt_p_pdot"] = p_pdot_panel(rec)
         if self._plt is None:
             path = (filename or f"cand_{idx:04d}") + ("" if str(filename).endswith(".npz") else ".npz")
             arrays = {k: v for k, v in p.items() if isinstance(v, np.ndarray)}
@@ -197,6 +232,8 @@ class CandidatePlotter:
         fig = self._draw(p)
         if "freq_phase" in p:
             self._draw_cube(fig, p)
+        if "opt_p_pdot" in p:
+            self._draw_opt(fig, p)
         fig.savefig(path)
         self._plt.close(fig)
         return path
@@ -284,6 +321,24 @@ class CandidatePlotter:
         tp_ax.set_title("Time-phase (filterbank fold)")
         tp_ax.set_ylabel("Subintegration")
         tp_ax.set_xlabel("Phase bin")
+
+    # the two cubeopt panels, in a further strip on the right
+    def _draw_opt(self, fig, p: Dict[str, object]) -> None:
+        w, h = fig.get_size_inches()
+        for ax in fig.axes:  # squeeze what is there into the old width
+            x0, y0, ww, hh = ax.get_position().bounds
+            ax.set_position([x0 * w / (w + 4.0), y0, ww * w / (w + 4.0), hh])
+        fig.set_size_inches(w + 4.0, h)
+        left = w / (w + 4.0) + 0.03
+        dm_ax = fig.add_axes([left, 0.55, 0.98 - left, 0.33])
+        pp_ax = fig.add_axes([left, 0.10, 0.98 - left, 0.33])
+        dm_ax.plot(p["opt_dms"], p["opt_dm_snr"])
+        dm_ax.set_title("S/N against DM (cube search)")
+        dm_ax.set_xlabel("DM (pc cm^-3)")
+        pp_ax.imshow(p["opt_p_pdot"], aspect="auto", interpolation="nearest", origin="lower")
+        pp_ax.set_title("P-Pdot plane (cube search)")
+        pp_ax.set_xlabel("Period trial")
+        pp_ax.set_ylabel("Acceleration trial")
 
 
 def plot_all(outdir: str, limit: int = 100, dest: Optional[str] = None) -> List[str]:

@@ -752,3 +752,195 @@ def rfi_clean(values: np.ndarray, block: int, nbits: int, killmask=None, thresh:
     S1, S2 = rfi_block_sums(values, block)
     mask = rfi_flag(S1, S2, values.shape[1], block, killmask, thresh, chan_frac, block_frac)
     return rfi_apply(values, mask, block, nbits, zero_dm), mask
+
+
+# --------------------------------------------------------------- cubeopt ----
+# NumPy oracle of csrc/include/psoup/cubeopt.hpp, written from its definition.
+OPT_MAX_PLANE = 16384
+
+
+def cube_opt_nwidths(nbins: int) -> int:
+    nw, w = 1, 2
+    while w <= nbins // 2:
+        nw, w = nw + 1, w * 2
+    return nw
+
+
+def cube_opt_prepare(sums, hits, nactive, ndm: int, np_: int, npd: int, k: int = 0,
+                     period: float = 1.0, dm: float = 0.0, acc: float = 0.0) -> Dict:
+    """Step 1: dict(d int32 [nints, nsub, nbins], mtot, v2 (Python ints), v).
+    Raises ValueError naming ``candidate k`` where the definition refuses."""
+    sums = np.asarray(sums, dtype=np.int64)
+    hits = np.asarray(hits, dtype=np.int64)
+    nactive = np.asarray(nactive)
+    nints, nsub, nbins = sums.shape
+    who = f"cube opt: candidate {k} "
+    if hits.shape != (nints, nbins) or nactive.shape != (nsub,):
+        raise ValueError(who + "has the wrong shape")
+    if (hits <= 0).any():
+        raise ValueError(who + "has a phase bin without samples")
+    if nints * nbins > OPT_MAX_PLANE:
+        raise ValueError(who + f"nints * nbins exceeds {OPT_MAX_PLANE}")
+    if ndm * np_ * npd * nbins >= 2 ** 31:
+        raise ValueError(who + "the trial bins do not fit 31 bits")
+    if not (math.isfinite(period) and period > 0 and math.isfinite(dm) and math.isfinite(acc)):
+        raise ValueError(who + "bad period, DM or acceleration")
+    href = hits.max(axis=1)
+    # exact integers throughout: Python ints in object arrays
+    S = sums.astype(object)
+    H = hits.astype(object)[:, None, :]
+    t = 2 * S * href.astype(object)[:, None, None]
+    if max(abs(int(t.max())), abs(int(t.min()))) >= 2 ** 63:
+        raise ValueError(who + "2 * sums * Href does not fit 63 bits")
+    q = (t + H) // (2 * H)
+    B = q.sum(axis=2) // nbins
+    d = q - B[:, :, None]
+    live = nactive > 0
+    d[:, ~live, :] = 0
+    maxabs = max(abs(int(d.max())), abs(int(d.min())))
+    if maxabs >= 2 ** 31 or int(d.min()) < -2 ** 31:
+        raise ValueError(who + "a baseline-subtracted value does not fit int32")
+    if maxabs * nints * int(live.sum()) * (nbins // 2) >= 2 ** 31:
+        raise ValueError(who + "the box sums do not fit int32")
+    mtot = int(d.sum())
+    v2 = int((d * d).sum())
+    return {"d": d.astype(np.int32), "mtot": mtot, "v2": v2, "v": float(v2) / float(nbins)}
+
+
+def _opt_reduce(x: float, nbins: int) -> int:
+    return int(np.rint(x)) % nbins
+
+
+def cube_opt_shifts(nints: int, nsub: int, nbins: int, nchans: int, tsamp: float, period: float, dm: float,
+                    delays: np.ndarray, ndm: int, np_: int, npd: int, dm_half_range: float = 0.0,
+                    p_step: float = 1.0, pd_step: float = 1.0) -> Dict:
+    """Step 2: dict(dms float32 [ndm], sdm int32 [ndm, nsub], st int32 [np, npd, nints])."""
+    dms = burst_dms(dm, ndm, dm_half_range)
+    delays = np.asarray(delays, dtype=np.float32)
+    sub_of = (np.arange(nchans, dtype=np.int64) * nsub) // nchans
+    tbp = float(np.float32(tsamp)) / float(period)
+    dm0 = float(np.float32(dm))
+    sdm = np.zeros((ndm, nsub), dtype=np.int32)
+    for s in range(nsub):
+        ch = np.nonzero(sub_of == s)[0]
+        dsub = 0.5 * (float(delays[ch[0]]) + float(delays[ch[-1]]))
+        for kd in range(ndm):
+            sdm[kd, s] = _opt_reduce((float(dms[kd]) - dm0) * dsub * tbp * nbins, nbins)
+    st = np.zeros((np_, npd, nints), dtype=np.int32)
+    for kp in range(np_):
+        L = (kp - np_ // 2) * float(p_step)
+        for kpd in range(npd):
+            Q = (kpd - npd // 2) * float(pd_step)
+            for i in range(nints):
+                u = (i + 0.5) / nints
+                st[kp, kpd, i] = _opt_reduce(L * (u - 0.5) + Q * (4.0 * u * (1.0 - u)), nbins)
+    return {"dms": dms, "sdm": sdm, "st": st}
+
+
+def cube_opt_profile(d: np.ndarray, sdm_row: np.ndarray, st_row: np.ndarray) -> np.ndarray:
+    """prof int64 [nbins] of one trial."""
+    nints, nsub, nbins = d.shape
+    b = np.arange(nbins)
+    A = np.zeros((nints, nbins), dtype=np.int64)
+    for s in range(nsub):
+        A += d[:, s, (b + int(sdm_row[s])) % nbins]
+    prof = np.zeros(nbins, dtype=np.int64)
+    for i in range(nints):
+        prof += A[i, (b + int(st_row[i])) % nbins]
+    return prof
+
+
+def cube_opt_search(d: np.ndarray, sdm: np.ndarray, st: np.ndarray) -> Dict:
+    """Step 3 from the definition: dict(best_val, best_idx, centre int32 [nw];
+    dmcurve int32 [nw, ndm]; ppd int32 [nw, np, npd])."""
+    d = np.asarray(d).astype(np.int64)
+    sdm, st = np.asarray(sdm), np.asarray(st)
+    nints, nsub, nbins = d.shape
+    ndm, (np_, npd) = sdm.shape[0], st.shape[:2]
+    nw = cube_opt_nwidths(nbins)
+    b = np.arange(nbins)
+    S = np.zeros((nw, ndm, np_ * npd, nbins), dtype=np.int64)
+    rot = (b[None, None, :] + st.reshape(np_ * npd, nints)[:, :, None]) % nbins  # [trial, i, b]
+    for kd in range(ndm):
+        A = np.zeros((nints, nbins), dtype=np.int64)
+        for s in range(nsub):
+            A += d[:, s, (b + int(sdm[kd, s])) % nbins]
+        prof = np.zeros((np_ * npd, nbins), dtype=np.int64)
+        for i in range(nints):
+            prof += A[i][rot[:, i, :]]
+        box = prof
+        for k in range(nw):
+            S[k, kd] = box
+            box = box + np.roll(box, -(1 << k), axis=1)
+    assert np.abs(S).max(initial=0) < 2 ** 31
+    flat = S.reshape(nw, -1)
+    return {"best_val": flat.max(axis=1).astype(np.int32),
+            "best_idx": flat.argmax(axis=1).astype(np.int32),  # the first occurrence
+            "dmcurve": S.max(axis=(2, 3)).astype(np.int32),
+            "ppd": S.max(axis=(1, 3)).reshape(nw, np_, npd).astype(np.int32),
+            "centre": S[:, ndm // 2, (np_ // 2) * npd + npd // 2].max(axis=1).astype(np.int32)}
+
+
+def cube_opt_snr(s: float, w: int, mtot: int, v: float, nbins: int) -> float:
+    if not v > 0:
+        return 0.0
+    return (float(s) - w * float(mtot) / nbins) / math.sqrt(v * w * (1.0 - float(w) / nbins))
+
+
+def cube_opt_finish(prep: Dict, shifts: Dict, found: Dict, period: float, acc: float, tsamp: float, fold_nsamps: int,
+                    p_step: float = 1.0, pd_step: float = 1.0) -> Dict:
+    """Step 4: the record of one candidate (the search outputs included)."""
+    d = prep["d"]
+    nints, nsub, nbins = d.shape
+    ndm = len(shifts["dms"])
+    np_, npd = shifts["st"].shape[:2]
+    nw = cube_opt_nwidths(nbins)
+
+    def best_of(vals):
+        best, which = 0.0, 0
+        for k in range(nw):
+            s = cube_opt_snr(float(int(vals[k])), 1 << k, prep["mtot"], prep["v"], nbins)
+            if k == 0 or s > best:
+                best, which = s, k
+        return best, which
+
+    snr, kbest = best_of(found["best_val"])
+    snr_in, _ = best_of(found["centre"])
+    flags = 0
+    if float(shifts["dms"][0]) == 0.0:
+        snr_dm0, _ = best_of(found["dmcurve"][:, 0])
+    else:
+        snr_dm0, flags = 0.0, 1
+    idx = int(found["best_idx"][kbest])
+    opt_bin, t = idx % nbins, idx // nbins
+    kpd, kp, kd = t % npd, (t // npd) % np_, t // npd // np_
+    L = (kp - np_ // 2) * float(p_step)
+    Q = (kpd - npd // 2) * float(pd_step)
+    ts = float(np.float32(tsamp))
+    n = float(int(fold_nsamps))
+    T = n * ts
+    out = {k: np.asarray(v).copy() for k, v in found.items()}
+    out.update(snr=snr, snr_in=snr_in, snr_dm0=snr_dm0,
+               opt_period=1.0 / (1.0 / float(period) - L / (nbins * T)),
+               opt_acc=float(np.float32(acc)) - (8.0 * C_LIGHT * Q * float(period)) / (nbins * ts * ts * n * n),
+               opt_dm=float(shifts["dms"][kd]), opt_width=1 << kbest, opt_bin=opt_bin, opt_kd=kd, opt_kp=kp,
+               opt_kpd=kpd, flags=flags, mtot=prep["mtot"], v=prep["v"], dms=np.asarray(shifts["dms"]).copy(),
+               profile=cube_opt_profile(d.astype(np.int64), shifts["sdm"][kd], shifts["st"][kp, kpd]).astype(np.int32))
+    return out
+
+
+def cube_optimise(cand: Dict, header: Dict, delays: np.ndarray, ndm: int = 64, np_: int = 65, npd: int = 33,
+                  dm_half_range: float = 0.0, p_step: float = 1.0, pd_step: float = 1.0, k: int = 0) -> Dict:
+    """The whole chain on one candidate dict (period, dm, acc, nactive, hits,
+    sums) of a fold-cube file with ``header``: cube_opt_finish's record plus
+    period, dm, acc."""
+    prep = cube_opt_prepare(cand["sums"], cand["hits"], cand["nactive"], ndm, np_, npd, k, float(cand["period"]),
+                            float(cand["dm"]), float(cand["acc"]))
+    nints, nsub, nbins = prep["d"].shape
+    sh = cube_opt_shifts(nints, nsub, nbins, int(header["nchans"]), float(header["tsamp"]), float(cand["period"]),
+                         float(cand["dm"]), delays, ndm, np_, npd, dm_half_range, p_step, pd_step)
+    found = cube_opt_search(prep["d"], sh["sdm"], sh["st"])
+    rec = cube_opt_finish(prep, sh, found, float(cand["period"]), float(cand["acc"]), float(header["tsamp"]),
+                          int(header["fold_nsamps"]), p_step, pd_step)
+    rec.update(period=float(cand["period"]), dm=float(np.float32(cand["dm"])), acc=float(np.float32(cand["acc"])))
+    return rec
