@@ -130,11 +130,17 @@ void bind_ffa(py::module_& m) {
 
   // Kernel driver for tests: FFA planes + per-profile best S/N of the
   // given base periods over a host series (ds, unit-variance bins of
-  // variance `var_per_bin`), on the current device.
+  // variance `var_per_bin`), on the current device.  `widths`: explicit
+  // boxcar ladder (empty: ffa_widths of the smallest period); `capacity`:
+  // size of the threshold-record buffer.  With `records` the result also
+  // carries the device counter (which may exceed capacity) and the first
+  // min(count, capacity) records as arrays period_idx, drift, snr, width.
   m.def(
       "ffa_fold_planes",
       [](py::array_t<float, py::array::c_style> ds, const std::vector<int>& periods, float var_per_bin,
-         float thresh) {
+         float thresh, const std::vector<int>& widths, uint32_t capacity, bool records) -> py::object {
+        PSOUP_CHECK(!periods.empty() && capacity >= 1, "ffa_fold_planes: no periods or no record capacity");
+        PSOUP_CHECK(widths.size() <= static_cast<size_t>(kern::kFfaMaxWidths), "ffa_fold_planes: width ladder");
         const uint64_t nds = static_cast<uint64_t>(ds.size());
         std::vector<kern::FfaPeriod> tab;
         uint64_t arena = 0, nprof = 0;
@@ -160,13 +166,14 @@ void bind_ffa(py::module_& m) {
         }
         DeviceBuffer<float> d_ds(nds), a0(arena), a1(arena), best(nprof);
         DeviceBuffer<kern::FfaPeriod> d_tab(tab.size());
-        DeviceBuffer<kern::FfaPeak> peaks(1u << 16);
+        DeviceBuffer<kern::FfaPeak> peaks(capacity);
         DeviceBuffer<uint32_t> cnt(1);
         PSOUP_HIP_CHECK(hipMemcpy(d_ds.data(), ds.data(), nds * 4, hipMemcpyHostToDevice));
         PSOUP_HIP_CHECK(
             hipMemcpy(d_tab.data(), tab.data(), tab.size() * sizeof(kern::FfaPeriod), hipMemcpyHostToDevice));
         PSOUP_HIP_CHECK(hipMemset(cnt.data(), 0, 4));
-        const std::vector<int> w = ffa_widths(*std::min_element(periods.begin(), periods.end()));
+        const std::vector<int> w =
+            widths.empty() ? ffa_widths(*std::min_element(periods.begin(), periods.end())) : widths;
         kern::FfaSnrParams sp{};
         sp.nwidths = static_cast<int32_t>(w.size());
         for (size_t i = 0; i < w.size(); ++i) sp.widths[i] = w[i];
@@ -175,7 +182,7 @@ void bind_ffa(py::module_& m) {
         kern::ffa_transform(d_ds.data(), d_tab.data(), static_cast<int>(tab.size()), max_m2, max_lg, max_p, a0.data(),
                             a1.data(), nullptr);
         kern::ffa_snr(d_tab.data(), static_cast<int>(tab.size()), max_m2, max_p, a0.data(), a1.data(), sp,
-                      peaks.data(), cnt.data(), 1u << 16, best.data(), nullptr);
+                      peaks.data(), cnt.data(), capacity, best.data(), nullptr);
         PSOUP_HIP_CHECK(hipDeviceSynchronize());
         std::vector<float> h0(arena), h1(arena), hb(nprof);
         PSOUP_HIP_CHECK(hipMemcpy(h0.data(), a0.data(), arena * 4, hipMemcpyDeviceToHost));
@@ -192,7 +199,23 @@ void bind_ffa(py::module_& m) {
           std::copy(hb.data() + fp.best_offset, hb.data() + fp.best_offset + fp.m2, b.mutable_data());
           out.append(py::make_tuple(fp.p, fp.m, fp.m2, plane, b));
         }
-        return py::make_tuple(out, w);
+        if (!records) return py::make_tuple(out, w);
+        uint32_t count = 0;
+        PSOUP_HIP_CHECK(hipMemcpy(&count, cnt.data(), 4, hipMemcpyDeviceToHost));
+        const size_t nrec = std::min(count, capacity);
+        std::vector<kern::FfaPeak> hp(nrec);
+        if (nrec)
+          PSOUP_HIP_CHECK(hipMemcpy(hp.data(), peaks.data(), nrec * sizeof(kern::FfaPeak), hipMemcpyDeviceToHost));
+        py::array_t<int32_t> r_period(nrec), r_drift(nrec), r_width(nrec);
+        py::array_t<float> r_snr(nrec);
+        for (size_t i = 0; i < nrec; ++i) {
+          r_period.mutable_data()[i] = hp[i].period_idx;
+          r_drift.mutable_data()[i] = hp[i].drift;
+          r_snr.mutable_data()[i] = hp[i].snr;
+          r_width.mutable_data()[i] = hp[i].width;
+        }
+        return py::make_tuple(out, w, count, r_period, r_drift, r_snr, r_width);
       },
-      py::arg("ds"), py::arg("periods"), py::arg("var_per_bin") = 1.0f, py::arg("thresh") = 1e30f);
+      py::arg("ds"), py::arg("periods"), py::arg("var_per_bin") = 1.0f, py::arg("thresh") = 1e30f,
+      py::arg("widths") = std::vector<int>(), py::arg("capacity") = 1u << 16, py::arg("records") = false);
 }

@@ -199,6 +199,12 @@ FfaCandidateList FfaEngine::search(const uint8_t* d_trial, float dm, int dm_idx)
       if (cnt)
         PSOUP_HIP_CHECK(hipMemcpy(h_peaks_.data(), d_peaks_.data() + t * cap_, cnt * sizeof(kern::FfaPeak),
                                   hipMemcpyDeviceToHost));
+      // the records arrive in the order the atomics landed: put them in
+      // (period, drift) order so that equal S/N values cluster the same way
+      // on every run
+      std::sort(h_peaks_.begin(), h_peaks_.end(), [](const kern::FfaPeak& a, const kern::FfaPeak& b) {
+        return a.period_idx != b.period_idx ? a.period_idx < b.period_idx : a.drift < b.drift;
+      });
       for (const auto& pk : h_peaks_) {
         const kern::FfaPeriod& fp = ch.periods[static_cast<size_t>(pk.period_idx)];
         const double pbins = fp.m2 > 1 ? fp.p + static_cast<double>(pk.drift) / (fp.m2 - 1) : fp.p;

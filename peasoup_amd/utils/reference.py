@@ -446,6 +446,126 @@ def ffa_downsample(x: np.ndarray, f: float) -> np.ndarray:
     return I[1:] - I[:-1]
 
 
+# Exact FFA oracles.  The FFA only adds: on integer-valued input every float32
+# partial sum of the kernels is an exact integer (below 2^24), so planes and
+# boxcar sums must equal these int64 results bit for bit.
+def ffa_transform_exact(X: np.ndarray) -> np.ndarray:
+    """ffa_transform on an integer [m2, P] matrix in int64, stage by stage:
+    stage st merges transformed blocks of q = 2^st rows into blocks of 2q with
+    one row gather and one add (fast at m2 = 2^17)."""
+    X = np.asarray(X)
+    assert X.ndim == 2 and np.issubdtype(X.dtype, np.integer), "integer [m2, P] matrix"
+    m2, P = X.shape
+    assert m2 >= 1 and m2 & (m2 - 1) == 0, "rows must be a power of two"
+    cur = X.astype(np.int64)
+    r = np.arange(m2)
+    cols = np.arange(P)
+    q = 1
+    while q < m2:
+        s = r & (2 * q - 1)  # row within its output block
+        h = (r - s) + (s >> 1)  # head-half source row; the tail-half one is q further
+        sh = ((s + 1) >> 1) % P
+        idx = (cols[None, :] + sh[:, None]) % P
+        cur = cur[h] + np.take_along_axis(cur[h + q], idx, axis=1)
+        q *= 2
+    return cur
+
+
+def ffa_fold_matrix_exact(ds: np.ndarray, P: int) -> np.ndarray:
+    """ffa_fold_matrix of an integer series, in int64."""
+    ds = np.asarray(ds)
+    m = len(ds) // P
+    m2 = 1
+    while m2 < m:
+        m2 *= 2
+    X = np.zeros((m2, P), dtype=np.int64)
+    X[:m] = ds[: m * P].astype(np.int64).reshape(m, P)
+    return X
+
+
+def ffa_boxcar_snr(planes: np.ndarray, widths, var: float) -> Tuple[List[int], np.ndarray]:
+    """(used widths, snr[len(used), m2]) in float64 of the [m2, P] profiles:
+    snr = max over circular phases of the boxcar sum / sqrt(w var), for every
+    ladder width that passes the w < P cut.  Exact sums on integer planes."""
+    p = np.asarray(planes)
+    if not np.issubdtype(p.dtype, np.integer):
+        p = p.astype(np.float64)
+    P = p.shape[1]
+    c = np.concatenate([np.zeros((p.shape[0], 1), dtype=p.dtype), np.cumsum(np.concatenate([p, p], axis=1), axis=1)],
+                       axis=1)
+    used = [int(w) for w in widths if w < P]
+    snr = np.empty((len(used), p.shape[0]), dtype=np.float64)
+    for k, w in enumerate(used):
+        snr[k] = (c[:, w: w + P] - c[:, :P]).max(axis=1) / np.sqrt(np.float64(w) * np.float64(var))
+    return used, snr
+
+
+def ffa_search_oracle(u8: np.ndarray, params, min_snr: Optional[float] = None, dense: Optional[List[Dict]] = None):
+    """Oracle of FfaEngine.search for inputs on which the engine is exact.
+
+    Octaves, chunks and periods come from _C.ffa_plan(params, n); detrend
+    (sp_trend over the engine's window), mean / standard deviation and the
+    per-profile S/N are float64, the normalised series, the downsampled series
+    and the planes int64.  Raises ValueError unless the normalised series is
+    integer-valued and every octave factor an integer.
+
+    Returns (dense, raw, candidates).  dense: one dict per (octave, chunk,
+    period index) with P, m, m2, factor, the used widths and snr[width, drift];
+    pass it back in to threshold again without recomputing.  raw (None when
+    min_snr is None): the records with best S/N > float32(min_snr) in (octave,
+    chunk, period index, drift) order, as dicts with period
+    (P + drift / (m2 - 1)) * factor * tsamp, the float64 snr, the narrowest
+    best width, nbins, octave and the per-width snr.  candidates:
+    _C.ffa_cluster of raw (S/N rounded to float32)."""
+    from peasoup_amd import _C as C
+
+    u8 = np.asarray(u8, dtype=np.uint8)
+    n = len(u8)
+    if dense is None:
+        window = int(math.ceil((params.detrend_s if params.detrend_s > 0 else 3.0 * params.p_end) / params.tsamp))
+        window = min(max(window, 64), n)
+        x = u8.astype(np.float64) - sp_trend(u8, window)
+        mean = x.mean()
+        std = math.sqrt(max((x * x).mean() - mean * mean, 0.0))
+        xn = (x - mean) / std
+        if not np.array_equal(xn, np.rint(xn)):
+            raise ValueError("ffa_search_oracle: the normalised series is not integer-valued")
+        xi = np.rint(xn).astype(np.int64)
+        dense = []
+        for o, oc in enumerate(C.ffa_plan(params, n)):
+            f = int(oc["factor"])
+            if f != oc["factor"]:
+                raise ValueError("ffa_search_oracle: octave factor %r is not an integer" % oc["factor"])
+            nds = int(oc["nds"])
+            ds = xi[: nds * f].reshape(nds, f).sum(axis=1)
+            for ci, ch in enumerate(oc["chunks"]):
+                for pi, (P, m, m2, lg, off) in enumerate(ch["periods"]):
+                    plane = ffa_transform_exact(ffa_fold_matrix_exact(ds, P))
+                    assert plane.shape == (m2, P) and m == nds // P
+                    used, snr = ffa_boxcar_snr(plane, C.ffa_widths(C.ffa_base_bins(params)), float(m) * float(f))
+                    dense.append(dict(octave=o, chunk=ci, period_idx=pi, P=P, m=m, m2=m2, factor=float(f),
+                                      widths=used, snr=snr))
+    if min_snr is None:
+        return dense, None, None
+    thresh = float(np.float32(min_snr))
+    raw = []
+    for d in dense:
+        best = d["snr"].max(axis=0)
+        arg = d["snr"].argmax(axis=0)  # first maximum: the narrowest width
+        for s in np.nonzero(best > thresh)[0]:
+            pbins = d["P"] + float(s) / (d["m2"] - 1) if d["m2"] > 1 else float(d["P"])
+            raw.append(dict(period=pbins * (d["factor"] * params.tsamp), snr=float(best[s]),
+                            width=d["widths"][int(arg[s])], nbins=d["P"], octave=d["octave"], drift=int(s),
+                            widths=d["widths"], snr_by_width=d["snr"][:, s]))
+    cands = []
+    for r in raw:
+        c = C.FfaCandidate()
+        c.period, c.snr, c.width, c.nbins, c.octave = r["period"], r["snr"], r["width"], r["nbins"], r["octave"]
+        cands.append(c)
+    tobs = n * params.tsamp
+    return dense, raw, C.ffa_cluster(cands, params.cluster_tol / tobs)
+
+
 # ------------------------------------------------------- single pulses ------
 # Float64 oracle of the single-pulse search, written from its definition
 # (csrc/include/psoup/singlepulse.hpp), not from the kernel.
