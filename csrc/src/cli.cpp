@@ -3,6 +3,7 @@
 #include "psoup/cubeopt.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
+#include "psoup/scrunch.hpp"
 #include "psoup/singlepulse.hpp"
 
 #include <cstdlib>
@@ -572,6 +573,55 @@ bool parse_rfi_cmdline(RfiCmdLineOptions& a, const std::vector<std::string>& arg
   }
   if (!(a.rfi_thresh >= 0) || !(a.rfi_chan_frac >= 0) || !(a.rfi_block_frac >= 0)) {
     std::cerr << "Error: --rfi_thresh, --rfi_chan_frac and --rfi_block_frac must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_scrunch_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_filscrunch.fil", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_scrunch_cmdline(ScrunchCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_scrunch_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The scrunched filterbank (8 bits)", a.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_n("", "dm", "DM the channels of a subband are aligned to before they are added", a.dm),
+      val_n("", "nsub", "Output channels; must divide nchans (0 = nchans: no subbanding)", a.nsub),
+      val_n("", "tscrunch", "Input samples added per output sample (1..256)", a.tscrunch),
+      val_n("", "sigma_out", "Noise sigma of a typical subband in the 8-bit output", a.sigma_out),
+      val_s("", "kill_out", "Output killfile: one line per subband, 0 = not live", a.killoutfilename),
+      sw("", "plan", "Print 'dm_lo dm_hi tscrunch' per tier over [0, --dm_end] and exit", a.plan),
+      val_n("", "dm_end", "Last DM of the plan (--plan only)", a.dm_end),
+      sw("v", "verbose", "verbose mode: print the offsets, the scale and the live count", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup filscrunch extension - subband and time-scrunch a filterbank", nullptr,
+                  exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (!(a.dm >= 0) || !(a.dm < 1e9f)) {
+    std::cerr << "Error: --dm must be finite and non-negative" << std::endl;
+    return false;
+  }
+  if (a.nsub < 0) {
+    std::cerr << "Error: --nsub must be at least 1 (0 = nchans)" << std::endl;
+    return false;
+  }
+  if (a.tscrunch < 1 || a.tscrunch > 256) {
+    std::cerr << "Error: --tscrunch must be in 1..256" << std::endl;
+    return false;
+  }
+  if (!(a.sigma_out > 0) || !(a.sigma_out < 1e9)) {
+    std::cerr << "Error: --sigma_out must be positive" << std::endl;
+    return false;
+  }
+  if (a.plan && !(a.dm_end >= 0)) {
+    std::cerr << "Error: --plan needs a non-negative --dm_end" << std::endl;
     return false;
   }
   return true;

@@ -4,7 +4,8 @@ flags]`` for the single-pulse search, ``python -m peasoup_amd cube [foldcube
 flags]`` for the filterbank fold cubes of candidates, ``python -m peasoup_amd
 burst [burstcube flags]`` for the cutouts of single-pulse candidates, ``python
 -m peasoup_amd opt [cubeopt flags]`` for the DM / period / acceleration search
-on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision) -- the peasoup CLI as a
+on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
+scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -78,6 +79,8 @@ def main(argv=None) -> int:
         return _main_opt(["cubeopt"] + argv[2:])
     if len(argv) > 1 and argv[1] == "clean":
         return _main_clean(["rficlean"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "scrunch":
+        return _main_scrunch(["filscrunch"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -215,6 +218,30 @@ def _main_clean(argv) -> int:
     if mask is not None and args.verbose:
         print(f"RFI excision: {mask.flagged_chans} of {mask.nchans} channels, {mask.flagged_blocks} of {mask.nblk} "
               f"blocks, {mask.flagged_cells} of {mask.nchans * mask.nblk} cells flagged")
+    return 0
+
+
+def _main_scrunch(argv) -> int:
+    from . import _C
+    from .models.scrunch import print_plan, scrunch_filterbank
+
+    ok, exit_now, args = _C.parse_scrunch_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        if args.plan:
+            print_plan(args)
+            return 0
+        res = scrunch_filterbank(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("scrunch", e)
+    if res is not None and args.verbose:
+        print(f"filscrunch: {res['nout']} samples x {res['nsub']} subbands, mul {res['mul']}, sigma_ref "
+              f"{res['sigma_ref']:g}, {res['nlive']} of {res['nsub']} subbands live")
+        print("M: " + " ".join(str(int(m)) for m in res["M"]))
     return 0
 
 

@@ -7,7 +7,8 @@ travel with the source snapshot to a GPU box.
 
 ``python peasoup_amd/_build.py --sanitize address`` (or ``undefined`` /
 ``thread``) builds only the host unit tests under that sanitizer into
-``build-<sanitizer>/`` -> ``bin/psoup_unit_tests_<sanitizer>``.
+``build-<sanitizer>/`` -> ``bin/psoup_unit_tests_<sanitizer>``; with ``--target
+psoup_scrunch_unit_tests`` (or another host unit-test target) that one instead.
 """
 from __future__ import annotations
 
@@ -63,4 +64,7 @@ if __name__ == "__main__":
     san = ""
     if "--sanitize" in sys.argv:
         san = sys.argv[sys.argv.index("--sanitize") + 1]
-    build(verbose="-v" in sys.argv, clean="--clean" in sys.argv, sanitize=san)
+    target = "psoup_unit_tests"
+    if "--target" in sys.argv:  # psoup_rfi_unit_tests, psoup_opt_unit_tests, psoup_scrunch_unit_tests
+        target = sys.argv[sys.argv.index("--target") + 1]
+    build(verbose="-v" in sys.argv, clean="--clean" in sys.argv, sanitize=san, sanitize_target=target)

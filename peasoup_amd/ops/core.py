@@ -770,3 +770,73 @@ def rfi_clean(chan_major: torch.Tensor, nsamps: int, nbits: int, bias: int = 0, 
     mask = cleaner.clean(chan_major.data_ptr(), stride, nchans, int(nsamps), int(nbits), int(bias), kill, dst_ptr,
                          dst_stride)
     return (chan_major if out is None else out), mask
+
+
+# -------------------------------------------------------------- filscrunch --
+def scrunch_tile() -> int:
+    """Most output samples per workgroup of the scrunch_sums kernel (the tile
+    at scrunch factor f is ``_C.scrunch_tile_at(f)``; the statistics block is
+    ``_C.scrunch_stat_block()``)."""
+    return int(_C.scrunch_tile())
+
+
+def scrunch_sums(chan_major: torch.Tensor, nsamps: int, rel, tscrunch: int, nsub: int, nout: int, bias: int = 0,
+                 killmask=None):
+    """Subbanded, time-scrunched sums of int8 rows [nchans, stride] (raw sample
+    = stored value + ``bias``; the first ``nsamps`` samples of a row are
+    valid): ``A[s, u]`` = sum over the unkilled channels c of subband s and i
+    < tscrunch of ``x[c, tscrunch u + i + rel[c]]``.  Returns (A int32 [nsub,
+    nout], S1, S2 int64 [nsub, ceil(nout / 4096)], the exact block sums of A
+    and A^2; the kernel's uint64): exactly ``utils.reference.scrunch_sums``."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    nout, nsub = int(nout), int(nsub)
+    a_stride = (nout + 15) // 16 * 16
+    A = torch.empty((nsub, a_stride), dtype=torch.int32, device=chan_major.device)
+    nblk = -(-nout // int(_C.scrunch_stat_block()))
+    S1 = torch.empty((nsub, nblk), dtype=torch.int64, device=chan_major.device)
+    S2 = torch.empty_like(S1)
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    _C.scrunch_sums_raw(chan_major.data_ptr(), stride, int(nsamps), nchans, int(bias), int(tscrunch), nsub,
+                        np.asarray(rel, dtype=np.int32), kill, nout, A.data_ptr(), a_stride, S1.data_ptr(),
+                        S2.data_ptr(), _s())
+    return A[:, :nout], S1, S2
+
+
+def scrunch_quant(A: torch.Tensor, M, mul: int, live) -> torch.Tensor:
+    """Requantises int32 sums [nsub, nout] with one offset ``M[s]`` per subband
+    and one multiplier: ``clamp((((A - M) * mul + 32768) >> 16) + 128, 0,
+    255)``, 128 where ``live[s]`` is 0.  Returns int8 rows [nsub, stride]
+    holding y - 128 in ``pack_transpose``'s layout (stride a multiple of 16;
+    the first nout samples of a row are valid)."""
+    if not A.is_cuda or A.dtype != torch.int32 or A.dim() != 2:
+        raise ValueError("A must be an int32 HIP tensor [nsub, nout]")
+    nsub, nout = int(A.shape[0]), int(A.shape[1])
+    a_stride = (nout + 15) // 16 * 16
+    a = torch.zeros((nsub, a_stride), dtype=torch.int32, device=A.device)
+    a[:, :nout] = A
+    y = torch.empty((nsub, a_stride), dtype=torch.int8, device=A.device)
+    _C.scrunch_quant_raw(a.data_ptr(), a_stride, nsub, nout, np.asarray(M, dtype=np.int32),
+                         np.asarray(live, dtype=np.uint8), int(mul), y.data_ptr(), a_stride, _s())
+    return y
+
+
+def scrunch(chan_major: torch.Tensor, nsamps: int, nbits: int, delays, dm: float = 0.0, nsub: int = 0,
+            tscrunch: int = 1, sigma_out: float = 16.0, bias: int = 0, killmask=None, foff: float = -1.0,
+            budget_bytes: Optional[int] = None):
+    """filscrunch on int8 rows [nchans, stride]: sums, host scale, requantise
+    (``_C.Scruncher``).  Returns (y int8 [nsub, stride'] holding y - 128 in
+    ``pack_transpose``'s layout, the result dict: nout, M, mul, live, S1, S2,
+    nactive, rel, killmask, chunks, ...).  Integer-exact: equals
+    ``utils.reference``'s scrunch_sums / scrunch_scale / scrunch_quant.
+    Everything is validated before anything is launched (``NativeError``)."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    kw = {} if budget_bytes is None else {"budget_bytes": int(budget_bytes)}
+    scr = _C.Scruncher(chan_major.data_ptr(), stride, int(nsamps), nchans, int(nbits), int(bias), float(foff),
+                       [float(d) for d in delays], kill,
+                       _C.ScrunchParams(float(dm), int(nsub), int(tscrunch), float(sigma_out)), _s(), **kw)
+    y_stride = (int(scr.nout) + 255) // 256 * 256
+    y = torch.zeros((int(scr.nsub), y_stride), dtype=torch.int8, device=chan_major.device)
+    res = scr.run(y.data_ptr(), y_stride)
+    res["launches"] = int(scr.launches)
+    return y, res

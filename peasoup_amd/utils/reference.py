@@ -1064,3 +1064,161 @@ def cube_optimise(cand: Dict, header: Dict, delays: np.ndarray, ndm: int = 64, n
                           int(header["fold_nsamps"]), p_step, pd_step)
     rec.update(period=float(cand["period"]), dm=float(np.float32(cand["dm"])), acc=float(np.float32(cand["acc"])))
     return rec
+
+
+# -------------------------------------------------------------- filscrunch --
+# The oracle of csrc/include/psoup/scrunch.hpp, written from its definition.
+SCRUNCH_BLOCK = 4096
+
+
+def scrunch_offsets(dm: float, delays: np.ndarray, nsub: int) -> Tuple[np.ndarray, int]:
+    """Step 1: (rel int32 [nchans], R)."""
+    nchans = len(delays)
+    if nsub < 1 or nchans % nsub:
+        raise ValueError("nsub must divide nchans")
+    w = nchans // nsub
+    off = dm_offsets([dm], np.asarray(delays, dtype=np.float32))[0].astype(np.int64)
+    rel = off - off[np.arange(nchans) // w * w]
+    if (rel < 0).any():
+        raise ValueError("a channel leads its subband's first channel (foff must be < 0)")
+    return rel.astype(np.int32), int(rel.max())
+
+
+def scrunch_nout(nsamps: int, R: int, f: int) -> int:
+    return (nsamps - R) // f if nsamps > R else 0
+
+
+def scrunch_sums(values: np.ndarray, rel: np.ndarray, f: int, nsub: int, killmask=None, nvalid: int = None):
+    """Steps 2 and 3 on raw ``values`` [nsamps, nchans] (the first ``nvalid``
+    samples are valid, default all): A int64 [nsub, nout], nactive int32
+    [nsub], S1 and S2 uint64 [nsub, nblk]."""
+    nsamps, nchans = values.shape
+    nsamps = nsamps if nvalid is None else int(nvalid)
+    w = nchans // nsub
+    kill = np.ones(nchans, bool) if killmask is None else np.asarray(killmask) != 0
+    nout = scrunch_nout(nsamps, int(np.max(rel)), f)
+    if nout < 1:
+        raise ValueError("nout < 1")
+    A = np.zeros((nsub, nout), dtype=np.int64)
+    nactive = np.zeros(nsub, dtype=np.int32)
+    for c in np.nonzero(kill)[0]:
+        r = int(rel[c])
+        A[c // w] += values[r:r + f * nout, c].astype(np.int64).reshape(nout, f).sum(axis=1)
+        nactive[c // w] += 1
+    S1, S2 = scrunch_block_sums(A)
+    return A, nactive, S1, S2
+
+
+def scrunch_block_sums(A: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    nsub, nout = A.shape
+    nblk = -(-nout // SCRUNCH_BLOCK)
+    S1 = np.zeros((nsub, nblk), dtype=np.uint64)
+    S2 = np.zeros((nsub, nblk), dtype=np.uint64)
+    a = A.astype(np.uint64)
+    for b in range(nblk):
+        seg = a[:, b * SCRUNCH_BLOCK:(b + 1) * SCRUNCH_BLOCK]
+        S1[:, b] = seg.sum(axis=1, dtype=np.uint64)
+        S2[:, b] = (seg * seg).sum(axis=1, dtype=np.uint64)
+    return S1, S2
+
+
+def _median(v: List[float]) -> float:
+    v = sorted(v)
+    n = len(v)
+    return v[n // 2] if n & 1 else (v[n // 2 - 1] + v[n // 2]) / 2.0
+
+
+def scrunch_scale(S1: np.ndarray, S2: np.ndarray, nout: int, nactive, sigma_out: float = 16.0) -> Dict:
+    """Step 4: Python ints for the numerator, float64 otherwise."""
+    nsub, nblk = S1.shape
+    if nblk != -(-nout // SCRUNCH_BLOCK):
+        raise ValueError("S1 / S2 must be [nsub, ceil(nout / L)]")
+    lens = [SCRUNCH_BLOCK] * (nblk - 1) + [nout - (nblk - 1) * SCRUNCH_BLOCK]
+    M = np.zeros(nsub, dtype=np.int32)
+    live = np.zeros(nsub, dtype=np.uint8)
+    sig = []
+    for s in range(nsub):
+        m, v = [], []
+        for b, n in enumerate(lens):
+            s1, s2 = int(S1[s, b]), int(S2[s, b])
+            m.append(float(s1) / float(n))
+            v.append(float(n * s2 - s1 * s1) / float(n * n))
+        med_m, med_v = _median(m), _median(v)
+        M[s] = math.floor(med_m + 0.5)
+        if int(nactive[s]) > 0 and med_v > 0:
+            live[s] = 1
+            sig.append(math.sqrt(med_v))
+    if not sig:
+        raise ValueError("no live subband")
+    sigma_ref = _median(sig)
+    t = sigma_out / sigma_ref * 65536.0 + 0.5
+    mul = 2 ** 31 - 1 if not t < 2.0 ** 31 else (1 if t < 1.0 else math.floor(t))
+    return {"M": M, "live": live, "mul": int(mul), "sigma_ref": sigma_ref, "nlive": len(sig)}
+
+
+def scrunch_quant(A: np.ndarray, M, mul: int, live) -> np.ndarray:
+    """Step 5: uint8 [nsub, nout]."""
+    d = ((np.asarray(A, dtype=np.int64) - np.asarray(M, dtype=np.int64)[:, None]) * int(mul) + 32768) >> 16
+    y = np.clip(d + 128, 0, 255).astype(np.uint8)
+    y[np.asarray(live) == 0] = 128
+    return y
+
+
+def scrunch_plan(tsamp: float, fch1: float, foff: float, nchans: int, dm_end: float) -> List[Tuple[float, float, int]]:
+    """Step 7: (dm_lo, dm_hi, tscrunch) per tier over [0, dm_end]."""
+    nu = min(fch1, fch1 + float(nchans - 1) * foff) / 1000.0
+    unit = tsamp * (nu * nu * nu) / (8.3e-6 * abs(foff))
+    tiers = []
+    for k in range(7):
+        lo = 0.0 if k == 0 else float(1 << k) * unit
+        if k > 0 and not lo < dm_end:
+            break
+        nxt = float(2 << k) * unit
+        tiers.append((lo, dm_end if (k == 6 or not nxt < dm_end) else nxt, 1 << k))
+    return tiers
+
+
+def scrunch_header(hdr: Dict, nsub: int, f: int, dm: float, nout: int) -> Dict:
+    """Step 6: the output's header dict from the input's (a parsed header)."""
+    out = dict(hdr)
+    w = int(hdr["nchans"]) // nsub
+    out.update(nchans=nsub, foff=float(w) * float(hdr["foff"]), tsamp=float(f) * float(hdr["tsamp"]), nbits=8,
+               nsamples=nout if "nsamples" in hdr.get("_present", ()) else 0, refdm=float(np.float32(dm)))
+    return out
+
+
+def scrunch_filterbank(infile: str, outfile: str, dm: float = 0.0, nsub: int = 0, f: int = 1,
+                       sigma_out: float = 16.0, killmask=None, kill_out: str = None) -> Dict:
+    """The whole tool on the CPU: reads ``infile``, writes ``outfile`` (and the
+    subband killfile ``kill_out``); returns the scale dict plus A, y, nout,
+    rel and nactive."""
+    import os
+
+    from .sigproc import header_bytes, read_filterbank
+
+    fb = read_filterbank(infile)
+    hdr = fb.header
+    nchans = int(hdr["nchans"])
+    nsub = nsub or nchans
+    if hdr["foff"] >= 0:
+        raise ValueError("foff must be negative")
+    if not 1 <= f <= 256 or nchans % nsub or not sigma_out > 0 or dm < 0:
+        raise ValueError("bad scrunch parameters")
+    delays = delay_table(nchans, hdr["tsamp"], hdr["fch1"], hdr["foff"])
+    rel, R = scrunch_offsets(dm, delays, nsub)
+    A, nactive, S1, S2 = scrunch_sums(fb.data, rel, f, nsub, killmask)
+    V = (1 << int(hdr["nbits"])) - 1
+    if V * f * int(nactive.max()) >= 1 << 26:
+        raise ValueError("2^26 bound")
+    nout = A.shape[1]
+    sc = scrunch_scale(S1, S2, nout, nactive, sigma_out)
+    y = scrunch_quant(A, sc["M"], sc["mul"], sc["live"])
+    tmp = outfile + ".tmp"
+    with open(tmp, "wb") as fo:
+        fo.write(header_bytes(scrunch_header(hdr, nsub, f, dm, nout), keep_present=True))
+        fo.write(np.ascontiguousarray(y.T).tobytes())
+    os.replace(tmp, outfile)
+    if kill_out:
+        with open(kill_out, "w") as fo:
+            fo.write("".join("1\n" if v else "0\n" for v in sc["live"]))
+    return dict(sc, A=A, y=y, nout=nout, rel=rel, R=R, nactive=nactive, S1=S1, S2=S2)

@@ -80,7 +80,11 @@ def _w_str(s: str) -> bytes:
     return struct.pack("<i", len(b)) + b
 
 
-def header_bytes(hdr: Dict) -> bytes:
+def header_bytes(hdr: Dict, keep_present: bool = False) -> bytes:
+    """``keep_present``: also write the numeric keys that ``hdr["_present"]``
+    (a parsed header's list of the keys its file had) names although they are
+    zero, as the native writer does for a header it has read."""
+    present = set(hdr.get("_present", ())) if keep_present else set()
     out = [_w_str("HEADER_START")]
     order = ["telescope_id", "machine_id", "data_type", "rawdatafile", "source_name", "barycentric",
              "pulsarcentric", "az_start", "za_start", "src_raj", "src_dej", "tstart", "tsamp", "nbits",
@@ -89,7 +93,7 @@ def header_bytes(hdr: Dict) -> bytes:
     must = {"data_type", "tsamp", "nbits", "fch1", "foff", "nchans", "nifs"}
     for k in order:
         v = hdr.get(k, HEADER_DEFAULTS[k])
-        if k not in must and not v:
+        if k not in must and not v and (k in _STRING or k not in present):
             continue
         if k in _STRING:
             out.append(_w_str(k) + _w_str(str(v)))
