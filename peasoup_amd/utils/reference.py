@@ -73,6 +73,27 @@ def interbin(X: np.ndarray) -> np.ndarray:
     return np.sqrt(np.maximum(a, b)).astype(np.float32)
 
 
+def interbin64(X: np.ndarray) -> np.ndarray:
+    """``interbin`` from its definition in float64 (no rounding to complex64):
+    sqrt(max(|X_k|^2, 0.5 |X_k - X_{k-1}|^2)) with X_{-1} = 0."""
+    X = np.asarray(X, dtype=np.complex128)
+    prev = np.concatenate([[0j], X[:-1]])
+    d = X - prev
+    a = X.real * X.real + X.imag * X.imag
+    b = 0.5 * (d.real * d.real + d.imag * d.imag)
+    return np.sqrt(np.maximum(a, b))
+
+
+def q8(P: np.ndarray) -> np.ndarray:
+    """device_common.hpp dev::q8, the harmonic sum's screening byte of a
+    float32 P: v = rint(4p) + 128; bytes 0..253 = v - 1, 254 = v >= 255 or
+    NaN, 255 = v <= 0."""
+    with np.errstate(invalid="ignore"):
+        v = np.rint(P.astype(np.float32) * np.float32(4.0)) + np.float32(128.0)
+        q = np.where(np.isnan(v) | (v >= 255), 254, np.where(v <= 0, 255, v - 1))
+    return q.astype(np.uint8)
+
+
 def median_scrunch5(x: np.ndarray) -> np.ndarray:
     n = len(x)
     if n < 5:
@@ -167,6 +188,22 @@ def resample_ii(x: np.ndarray, af: float) -> np.ndarray:
     j = np.rint(i + i * af * (i - n))
     j = np.clip(j, 0, n - 1).astype(np.int64)
     return x[j]
+
+
+def half_spectrum(r: np.ndarray) -> np.ndarray:
+    """The Z that ``ops.fft4_resample_spectrum`` defines, in complex128: the
+    n/2-point FFT of the packed series z[m] = r[2m] + i r[2m+1]."""
+    r = np.asarray(r, dtype=np.float64)
+    return np.fft.fft(r[0::2] + 1j * r[1::2])
+
+
+def search_spectrum(x: np.ndarray, acc: float, tsamp: float, mean: float, sigma: float) -> np.ndarray:
+    """One acceleration trial's normalised search spectrum from its
+    definition, float64 throughout: resampleII -> real FFT -> interbinned
+    amplitude -> (amp - mean) / sigma.  Returns all n/2 + 1 bins."""
+    r = resample_ii(x, accel_factor(acc, tsamp))
+    X = np.fft.rfft(r.astype(np.float64))
+    return (interbin64(X) - float(mean)) / float(sigma)
 
 
 def resample_v1(x: np.ndarray, af: float) -> np.ndarray:

@@ -17,11 +17,7 @@ pytestmark = pytest.mark.gpu
 dev = "cuda"
 
 
-def _q8_ref(P):
-    with np.errstate(invalid="ignore"):
-        v = np.rint(P.astype(np.float32) * np.float32(4.0)) + np.float32(128.0)
-        q = np.where(np.isnan(v) | (v >= 255), 254, np.where(v <= 0, 255, v - 1))
-    return q.astype(np.uint8)
+from peasoup_amd.utils.reference import q8 as _q8_ref  # noqa: E402  (device_common.hpp dev::q8)
 
 
 def _series(log2n, seed, pulsar=False):
