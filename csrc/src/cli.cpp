@@ -1,6 +1,7 @@
 #include "psoup/cli.hpp"
 #include "psoup/burstcube.hpp"
 #include "psoup/cubeopt.hpp"
+#include "psoup/digi.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
 #include "psoup/scrunch.hpp"
@@ -622,6 +623,45 @@ bool parse_scrunch_cmdline(ScrunchCmdLineOptions& a, const std::vector<std::stri
   }
   if (a.plan && !(a.dm_end >= 0)) {
     std::cerr << "Error: --plan needs a non-negative --dm_end" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_digi_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_fildigi.fil", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_digi_cmdline(DigiCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_digi_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil of 8, 16 or 32 bits, either band order)", a.infilename, true),
+      val_s("o", "outfilename", "The digitised filterbank (8 bits, descending frequency)", a.outfilename),
+      val_s("k", "killfile", "Channel mask file (input channel order)", a.killfilename),
+      val_s("", "kill_out", "Output killfile (output channel order): 0 = killed or dead", a.killoutfilename),
+      val_n("", "sigma_out", "Noise sigma of a channel in the 8-bit output", a.sigma_out),
+      val_s("", "scale", "channel: one gain per channel (flattens the bandpass); file: one gain for all", a.scale),
+      val_n("", "rescale_blocks", "Blocks of 4096 samples per rescaling interval (0 = one for the file)",
+            a.rescale_blocks),
+      sw("v", "verbose", "verbose mode: print nbad, nclip, the live count and the range of gains", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup fildigi extension - digitise a 8/16/32-bit filterbank to 8 bits", nullptr,
+                  exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (!(a.sigma_out > 0) || !(a.sigma_out < 1e9)) {
+    std::cerr << "Error: --sigma_out must be positive" << std::endl;
+    return false;
+  }
+  if (a.scale != "channel" && a.scale != "file") {
+    std::cerr << "Error: --scale must be channel or file" << std::endl;
+    return false;
+  }
+  if (a.rescale_blocks < 0) {
+    std::cerr << "Error: --rescale_blocks must be non-negative" << std::endl;
     return false;
   }
   return true;

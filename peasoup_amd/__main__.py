@@ -5,7 +5,8 @@ flags]`` for the filterbank fold cubes of candidates, ``python -m peasoup_amd
 burst [burstcube flags]`` for the cutouts of single-pulse candidates, ``python
 -m peasoup_amd opt [cubeopt flags]`` for the DM / period / acceleration search
 on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
-scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank) -- the peasoup CLI as a
+scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``python -m peasoup_amd digi
+[fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -81,6 +82,8 @@ def main(argv=None) -> int:
         return _main_clean(["rficlean"] + argv[2:])
     if len(argv) > 1 and argv[1] == "scrunch":
         return _main_scrunch(["filscrunch"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "digi":
+        return _main_digi(["fildigi"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -242,6 +245,27 @@ def _main_scrunch(argv) -> int:
         print(f"filscrunch: {res['nout']} samples x {res['nsub']} subbands, mul {res['mul']}, sigma_ref "
               f"{res['sigma_ref']:g}, {res['nlive']} of {res['nsub']} subbands live")
         print("M: " + " ".join(str(int(m)) for m in res["M"]))
+    return 0
+
+
+def _main_digi(argv) -> int:
+    from . import _C
+    from .models.digi import digitise_filterbank
+
+    ok, exit_now, args = _C.parse_digi_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = digitise_filterbank(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("digi", e)
+    if res is not None and args.verbose:
+        print(f"fildigi: {res['nsamps']} samples x {res['nchans']} channels, nbad {int(res['nbad'].sum())}, nclip "
+              f"{res['nclip']}, {res['nlive']} of {res['nchans']} channels live, gains {res['gain_min']:g} to "
+              f"{res['gain_max']:g}")
     return 0
 
 

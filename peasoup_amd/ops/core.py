@@ -840,3 +840,78 @@ def scrunch(chan_major: torch.Tensor, nsamps: int, nbits: int, delays, dm: float
     res = scr.run(y.data_ptr(), y_stride)
     res["launches"] = int(scr.launches)
     return y, res
+
+
+# ----------------------------------------------------------------- fildigi --
+_DIGI_DTYPES = {torch.uint8: (8, False), torch.int8: (8, True), torch.uint16: (16, False), torch.float32: (32, False)}
+
+
+def _check_digi(x: torch.Tensor):
+    if not x.is_cuda or x.dim() != 2 or x.dtype not in _DIGI_DTYPES or not x.is_contiguous():
+        raise ValueError("x must be a contiguous HIP tensor [nsamps, nchans] of uint8, int8, uint16 or float32")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("x must hold at least one sample")
+    return (int(x.shape[0]), int(x.shape[1])) + _DIGI_DTYPES[x.dtype]
+
+
+def digi_block_sums(x: torch.Tensor):
+    """Exact block statistics of time-major samples [nsamps, nchans] (uint8,
+    int8, uint16 or float32) per channel and block of 4096 samples: a dict of
+    N (finite samples; the kernel's uint32 as int64), S1 int64, S2 (the
+    kernel's uint64 bits as int64), E int32 (the block quantum's exponent; 0
+    for integer input), all [nchans, nblk], and nbad int64 [nchans]: exactly
+    ``utils.reference.digi_block_sums``."""
+    nsamps, nchans, nbits, signed = _check_digi(x)
+    nblk = -(-nsamps // int(_C.digi_stat_block()))
+    N = torch.empty((nchans, nblk), dtype=torch.int32, device=x.device)
+    S1 = torch.empty((nchans, nblk), dtype=torch.int64, device=x.device)
+    S2 = torch.empty_like(S1)
+    E = torch.empty_like(N)
+    _C.digi_block_sums_raw(x.data_ptr(), nbits, signed, nsamps, nchans, N.data_ptr(), S1.data_ptr(), S2.data_ptr(),
+                           E.data_ptr(), _s())
+    N = N.to(torch.int64) & 0xFFFFFFFF
+    return {"N": N, "S1": S1, "S2": S2, "E": E, "nbad": nsamps - N.sum(dim=1)}
+
+
+def digi_quant(x: torch.Tensor, mean, gain, J: int = 0, flip: bool = False):
+    """Requantises time-major samples [nsamps, nchans] to 8 bits with explicit
+    tables ``mean`` and ``gain`` (float64 [nint, nchans], input channel order,
+    gain 0 = not live; interval of sample t: ``t // 4096 // J``, 0 for J = 0):
+    ``clamp(rint((x - mean) * gain) + 128, 0, 255)``, 128 for a non-finite
+    sample or a cell that is not live, the band reversed when ``flip``.
+    Returns (y uint8 [nsamps, nchans], nclip)."""
+    nsamps, nchans, nbits, signed = _check_digi(x)
+    total = nsamps * nchans
+    buf = torch.empty((total + 15) // 16 * 16, dtype=torch.uint8, device=x.device)
+    nclip = _C.digi_quant_raw(x.data_ptr(), nbits, signed, nsamps, nchans, int(J),
+                              np.ascontiguousarray(mean, dtype=np.float64).reshape(-1),
+                              np.ascontiguousarray(gain, dtype=np.float64).reshape(-1), bool(flip), buf.data_ptr(),
+                              _s())
+    return buf[:total].view(nsamps, nchans), int(nclip)
+
+
+def digitise(data: np.ndarray, foff: float, sigma_out: float = 16.0, scale: str = "channel", rescale_blocks: int = 0,
+             killmask=None, budget_bytes: Optional[int] = None):
+    """fildigi on host samples ``data`` [nsamps, nchans] (a NumPy array of
+    uint8, int8, uint16 or float32: the file, possibly larger than the device
+    budget): block sums, host scale, requantise (``_C.Digitiser``), in time
+    chunks of whole blocks.  Returns (y uint8 NumPy [nsamps, nchans] in output
+    channel order, the result dict: N, S1, S2, E, nbad, mean, gain, live,
+    killmask, nclip, chunks, launches, ...).  Equals ``utils.reference``'s
+    digi_block_sums / digi_scale / digi_quant.  Everything is validated before
+    anything is launched (``NativeError``)."""
+    kinds = {np.dtype(np.uint8): (8, False), np.dtype(np.int8): (8, True), np.dtype(np.uint16): (16, False),
+             np.dtype(np.float32): (32, False)}
+    data = np.ascontiguousarray(data)
+    if data.dtype not in kinds or data.ndim != 2:
+        raise ValueError("data must be [nsamps, nchans] of uint8, int8, uint16 or float32")
+    nbits, signed = kinds[data.dtype]
+    nsamps, nchans = data.shape
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    kw = {} if budget_bytes is None else {"budget_bytes": int(budget_bytes)}
+    dig = _C.Digitiser(data.reshape(-1).view(np.uint8), nbits, signed, int(nsamps), int(nchans), float(foff), kill,
+                       _C.DigiParams(float(sigma_out), str(scale), int(rescale_blocks)), _s(), **kw)
+    y, res = dig.run()
+    res["launches"] = int(dig.launches)
+    res["chunk_samples"] = int(dig.chunk_samples)
+    return y, res

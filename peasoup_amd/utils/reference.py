@@ -1259,3 +1259,160 @@ def scrunch_filterbank(infile: str, outfile: str, dm: float = 0.0, nsub: int = 0
         with open(kill_out, "w") as fo:
             fo.write("".join("1\n" if v else "0\n" for v in sc["live"]))
     return dict(sc, A=A, y=y, nout=nout, rel=rel, R=R, nactive=nactive, S1=S1, S2=S2)
+
+
+# ----------------------------------------------------------------- fildigi --
+# The oracle of csrc/include/psoup/digi.hpp, written from its definition.
+DIGI_BLOCK = 4096
+
+
+def digi_quantum(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Step 1 on one statistics block ``x`` [len, nchans]: (E int32 [nchans],
+    q int64 [len, nchans]; q is 0 at the non-finite samples of float input)."""
+    x = np.asarray(x)
+    nchans = x.shape[1]
+    if x.dtype != np.float32:
+        return np.zeros(nchans, np.int32), x.astype(np.int64)
+    bits = x.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    fin = (bits & np.uint32(0x7F800000)) != np.uint32(0x7F800000)
+    amax = np.where(fin, bits, np.uint32(0)).max(axis=0)
+    e = np.maximum((amax >> np.uint32(23)).astype(np.int32), 1)
+    E = np.where(amax == 0, 0, e - 127 - 22).astype(np.int32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.rint(np.ldexp(np.where(fin, x, np.float32(0)).astype(np.float64), -E[None, :]))
+    return E, q.astype(np.int64)
+
+
+def digi_block_sums(x: np.ndarray) -> Dict:
+    """Steps 1 and 2 on samples ``x`` [nsamps, nchans] (uint8, int8, uint16 or
+    float32): N uint32, S1 int64, S2 uint64, E int32, all [nchans, nblk], and
+    nbad uint64 [nchans]."""
+    x = np.asarray(x)
+    nsamps, nchans = x.shape
+    nblk = -(-nsamps // DIGI_BLOCK)
+    N = np.zeros((nchans, nblk), np.uint32)
+    S1 = np.zeros((nchans, nblk), np.int64)
+    S2 = np.zeros((nchans, nblk), np.uint64)
+    E = np.zeros((nchans, nblk), np.int32)
+    for b in range(nblk):
+        seg = x[b * DIGI_BLOCK:(b + 1) * DIGI_BLOCK]
+        fin = np.isfinite(seg) if seg.dtype == np.float32 else np.ones(seg.shape, bool)
+        E[:, b], q = digi_quantum(seg)
+        N[:, b] = fin.sum(axis=0)
+        S1[:, b] = q.sum(axis=0)
+        S2[:, b] = (q * q).astype(np.uint64).sum(axis=0, dtype=np.uint64)
+    nbad = (nsamps - N.astype(np.int64).sum(axis=1)).astype(np.uint64)
+    return {"N": N, "S1": S1, "S2": S2, "E": E, "nbad": nbad}
+
+
+def digi_nint(nblk: int, J: int) -> int:
+    return -(-nblk // J) if J > 0 else 1
+
+
+def digi_scale(N, S1, S2, E, killmask=None, sigma_out: float = 16.0, scale: str = "channel", J: int = 0) -> Dict:
+    """Steps 3 and 4: Python ints for the numerator, float64 otherwise,
+    ``numpy.median`` for the medians.  mean, gain float64 and live uint8, all
+    [nint, nchans] (gain and mean 0 where not live); alive [nchans]."""
+    if not sigma_out > 0 or J < 0 or scale not in ("channel", "file"):
+        raise ValueError("bad digi parameters")
+    nchans, nblk = N.shape
+    nint = digi_nint(nblk, J)
+    per = J if J > 0 else nblk
+    kill = np.ones(nchans, bool) if killmask is None or len(killmask) == 0 else np.asarray(killmask) != 0
+    mean = np.zeros((nint, nchans))
+    gain = np.zeros((nint, nchans))
+    sig = np.zeros((nint, nchans))
+    live = np.zeros((nint, nchans), np.uint8)
+    for c in range(nchans):
+        for j in range(nint):
+            m, v = [], []
+            for b in range(j * per, min(nblk, (j + 1) * per)):
+                n, s1, s2, e = int(N[c, b]), int(S1[c, b]), int(S2[c, b]), int(E[c, b])
+                if n == 0:
+                    continue
+                m.append(math.ldexp(float(s1) / float(n), e))
+                v.append(math.ldexp(float(n * s2 - s1 * s1) / float(n * n), 2 * e))
+            if not m:
+                continue
+            med_m, med_v = float(np.median(np.array(m))), float(np.median(np.array(v)))
+            if kill[c] and med_v > 0:
+                live[j, c] = 1
+                mean[j, c] = med_m
+                sig[j, c] = math.sqrt(med_v)
+    if not live.any():
+        raise ValueError("no live channel")
+    for j in range(nint):
+        on = live[j] != 0
+        if scale == "file":
+            if on.any():
+                gain[j, on] = sigma_out / float(np.median(sig[j, on]))
+        else:
+            gain[j, on] = sigma_out / sig[j, on]
+    alive = live.any(axis=0).astype(np.int64)
+    g = gain[live != 0]
+    return {"nint": nint, "mean": mean, "gain": gain, "live": live, "alive": alive, "nlive": int(alive.sum()),
+            "gain_min": float(g.min()), "gain_max": float(g.max())}
+
+
+def digi_quant(x: np.ndarray, mean, gain, J: int = 0, flip: bool = False) -> Tuple[np.ndarray, int]:
+    """Steps 5 and 6: (y uint8 [nsamps, nchans] in output order, nclip).
+    mean, gain [nint, nchans] in input channel order, gain 0 = not live."""
+    x = np.asarray(x)
+    nsamps, nchans = x.shape
+    mean = np.asarray(mean, np.float64).reshape(-1, nchans)
+    gain = np.asarray(gain, np.float64).reshape(-1, nchans)
+    blk = np.arange(nsamps) // DIGI_BLOCK
+    j = blk // J if J > 0 else np.zeros(nsamps, np.int64)
+    good = (np.isfinite(x) if x.dtype == np.float32 else np.ones(x.shape, bool)) & (gain[j] != 0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.rint((np.where(good, x, 0).astype(np.float64) - mean[j]) * gain[j]) + 128.0
+    r = np.where(good, r, 128.0)
+    nclip = int(((r < 0) | (r > 255)).sum())
+    y = np.clip(r, 0, 255).astype(np.uint8)
+    return (y[:, ::-1] if flip else y), nclip
+
+
+def digi_band(fch1: float, foff: float, nchans: int) -> Tuple[bool, float, float]:
+    """Step 6: (flip, fch1', foff')."""
+    if foff > 0:
+        return True, fch1 + float(nchans - 1) * foff, -foff
+    return False, fch1, foff
+
+
+def digi_header(hdr: Dict, nsamps: int) -> Dict:
+    """Step 7: the output's header dict from the input's (a parsed header)."""
+    out = dict(hdr)
+    _, fch1, foff = digi_band(float(hdr["fch1"]), float(hdr["foff"]), int(hdr["nchans"]))
+    present = [k for k in hdr.get("_present", ()) if k != "signed"]
+    out.update(nbits=8, signed=0, fch1=fch1, foff=foff, nsamples=nsamps if "nsamples" in present else 0)
+    out["_present"] = present
+    return out
+
+
+def digi_filterbank(infile: str, outfile: str, sigma_out: float = 16.0, scale: str = "channel", J: int = 0,
+                    killmask=None, kill_out: str = None) -> Dict:
+    """The whole tool on the CPU: reads ``infile``, writes ``outfile`` (and the
+    killfile ``kill_out`` in output channel order); returns the block tables,
+    the scale dict, y, nclip, flip and killmask."""
+    import os
+
+    from .sigproc import header_bytes, read_raw_filterbank
+
+    hdr, x = read_raw_filterbank(infile)
+    nsamps, nchans = x.shape
+    if nsamps < 1:
+        raise ValueError("shorter than one sample")
+    sums = digi_block_sums(x)
+    sc = digi_scale(sums["N"], sums["S1"], sums["S2"], sums["E"], killmask, sigma_out, scale, J)
+    flip = digi_band(float(hdr["fch1"]), float(hdr["foff"]), nchans)[0]
+    y, nclip = digi_quant(x, sc["mean"], sc["gain"], J, flip)
+    kill = sc["alive"][::-1] if flip else sc["alive"]
+    tmp = outfile + ".tmp"
+    with open(tmp, "wb") as fo:
+        fo.write(header_bytes(digi_header(hdr, nsamps), keep_present=True))
+        fo.write(np.ascontiguousarray(y).tobytes())
+    os.replace(tmp, outfile)
+    if kill_out:
+        with open(kill_out, "w") as fo:
+            fo.write("".join("1\n" if v else "0\n" for v in kill))
+    return dict(sums, **sc, y=y, nclip=nclip, flip=flip, killmask=[int(v) for v in kill])

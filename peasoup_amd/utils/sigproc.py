@@ -172,6 +172,50 @@ def write_filterbank(path: str, header: Dict, values: np.ndarray) -> None:
         f.write(pack_samples(values, int(hdr["nbits"])).tobytes())
 
 
+def raw_dtype(nbits: int, signed: int = 0):
+    """Sample type of an 8 / 16 / 32-bit filterbank: uint8 (int8 when the
+    header's ``signed`` is 1), little-endian uint16, little-endian float32."""
+    if nbits == 8:
+        return np.dtype(np.int8) if signed else np.dtype(np.uint8)
+    if nbits == 16:
+        return np.dtype("<u2")
+    if nbits == 32:
+        return np.dtype("<f4")
+    raise ValueError(f"nbits must be 8, 16 or 32, got {nbits}")
+
+
+def read_raw_filterbank(path: str):
+    """(header, samples [nsamps, nchans]) of a filterbank of 8 (signed or not),
+    16 or 32 bits, as ``fildigi`` reads it: whole samples only, nsamples
+    capped by the file's size."""
+    import os
+
+    hdr = read_header(path)
+    dt = raw_dtype(int(hdr["nbits"]), int(hdr["signed"]))
+    nchans = int(hdr["nchans"])
+    avail = (os.path.getsize(path) - hdr["size"]) // (nchans * dt.itemsize)
+    nsamps = min(int(hdr["nsamples"]), avail) if hdr["nsamples"] > 0 else avail
+    data = np.fromfile(path, dtype=dt, count=nsamps * nchans, offset=hdr["size"])
+    return hdr, data.reshape(nsamps, nchans)
+
+
+def write_raw_filterbank(path: str, header: Dict, values: np.ndarray, with_nsamples: bool = True) -> None:
+    """Writes ``values`` [nsamps, nchans] of dtype uint8, int8, uint16 or
+    float32 with nbits and ``signed`` set from the dtype."""
+    v = np.asarray(values)
+    kinds = {np.dtype(np.uint8): (8, 0), np.dtype(np.int8): (8, 1), np.dtype(np.uint16): (16, 0),
+             np.dtype(np.float32): (32, 0)}
+    if v.dtype not in kinds or v.ndim != 2:
+        raise ValueError("values must be [nsamps, nchans] of uint8, int8, uint16 or float32")
+    hdr = dict(header)
+    hdr["nbits"], hdr["signed"] = kinds[v.dtype]
+    hdr["nchans"] = int(v.shape[1])
+    hdr["nsamples"] = int(v.shape[0]) if with_nsamples else 0
+    with open(path, "wb") as f:
+        f.write(header_bytes(hdr))
+        f.write(np.ascontiguousarray(v.astype(v.dtype.newbyteorder("<"), copy=False)).tobytes())
+
+
 def read_tim(path: str):
     hdr = read_header(path)
     dtype = {32: np.float32, 8: np.uint8}[hdr["nbits"]]

@@ -130,6 +130,38 @@ def write(path: str, nsamps: int, header: Optional[Dict] = None, pulsars=(), see
     return hdr
 
 
+def as_raw(values: np.ndarray, header: Dict, dtype="float32", decades: float = 4.0, drift: float = 0.0,
+           ascending: bool = False, seed: int = 0) -> Tuple[Dict, np.ndarray]:
+    """Turns generated samples ``values`` [nsamps, nchans] (uint8, descending
+    band) into the data of a backend that writes float32 or uint16: channel c
+    becomes ``gain[c] * (values - mid) * (1 + drift * t / nsamps) + offset[c]``
+    with seeded per-channel gains spread log-uniformly over ``decades`` decades
+    and offsets of a few sigma, a slow baseline drift, and optionally the band
+    stored lowest frequency first.  Returns (header, samples); the header has
+    the new nbits, fch1 and foff.  uint16 output is rounded and clipped."""
+    rng = np.random.default_rng(seed)
+    nsamps, nchans = values.shape
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.uint16)):
+        raise ValueError("dtype must be float32 or uint16")
+    mid = ((1 << int(header["nbits"])) - 1) / 2.0
+    gains = 10.0 ** (rng.uniform(-0.5, 0.5, nchans) * decades)
+    offsets = gains * rng.uniform(-3.0, 3.0, nchans) * max(mid / 2.0, 0.5)
+    if dt == np.dtype(np.uint16):
+        gains = gains / gains.max() * 64.0          # sigma of at most ~4000 counts
+        offsets = 20000.0 + offsets / np.abs(offsets).max() * 5000.0
+    ramp = 1.0 + drift * np.arange(nsamps, dtype=np.float64)[:, None] / max(nsamps, 1)
+    x = (values.astype(np.float64) - mid) * gains[None, :] * ramp + offsets[None, :] * ramp
+    x = np.clip(np.rint(x), 0, 65535).astype(np.uint16) if dt == np.dtype(np.uint16) else x.astype(np.float32)
+    hdr = dict(header)
+    hdr["nbits"] = 8 * dt.itemsize
+    if ascending:
+        x = np.ascontiguousarray(x[:, ::-1])
+        hdr["fch1"] = float(header["fch1"]) + float(nchans - 1) * float(header["foff"])
+        hdr["foff"] = -float(header["foff"])
+    return hdr, x
+
+
 def packed(nsamps: int, header: Dict, pulsars=(), seed: int = 0, bursts=(), rfi=()) -> np.ndarray:
     return pack_samples(generate(nsamps, header, pulsars, seed, bursts=bursts, rfi=rfi), int(header["nbits"]))
 
