@@ -221,8 +221,13 @@ class Whitener {
   // allow_fft4: run the N-point real transforms on the four-step FFT passes
   // (K = 1) when the geometry allows; otherwise (or when false) rocFFT.
   Whitener(uint64_t n, float tsamp, hipStream_t stream, bool allow_fft4 = true);
-  // trial u8[nsamps] -> d_series f32[n] (pad with mean / truncate)
-  void load_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series);
+  // trial u8[nsamps] -> d_series f32[n] (pad with mean / truncate); centre: every value less rint(mean)
+  // (kernels.hpp f32_centre) -- after forward(), restore_dc() gives X_0 its n rint(mean) back
+  void load_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series, bool centre = false);
+  void restore_dc(float2* d_spec);
+  // load_trial (centred) + R2C + restore_dc + running median, deredden (+zap), [stats to d_stats] + C2R
+  void whiten_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series, const uint32_t* d_zapmask,
+                    float* d_stats, float boundary5, float boundary25);
   // R2C, running median, deredden (+zap), [interbin stats], C2R in place.
   void whiten(float* d_series, const uint32_t* d_zapmask, bool with_stats, float boundary5, float boundary25);
   // load_trial + whiten (with stats) for `count` trials in one batch: trial b
@@ -286,7 +291,9 @@ class Whitener {
   DeviceBuffer<float> m5_, m25_, m125_;
   DeviceBuffer<double> partials_;
   DeviceBuffer<float> stats_;
+  DeviceBuffer<float> cstat_;  // whiten: {mean, rms, std} of the input series, [3] the offset taken off
   DeviceBuffer<unsigned long long> sum_;
+  uint64_t loaded_nvalid_ = 0;  // nvalid of the last load_trial (sum_ is its sum)
 };
 
 struct SearchCounters {

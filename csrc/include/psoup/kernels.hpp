@@ -159,9 +159,18 @@ void dedisperse_lds(const int8_t* chan_major, uint64_t chan_stride, const int32_
 // count > 1: rows b at in + b*in_stride, sums sum[b], outputs out + b*out_stride.
 void u8_sum(const uint8_t* in, uint64_t n, unsigned long long* sum, hipStream_t s, int count = 1,
             uint64_t in_stride = 0);
-// out[i] = i < nvalid ? in[i] : (float)(sum / nvalid)
+// out[i] = i < nvalid ? in[i] : (float)(sum / nvalid); centre: every value less rint of that mean (exact)
 void u8_to_f32_pad(const uint8_t* in, uint64_t nvalid, float* out, uint64_t n, const unsigned long long* sum,
-                   hipStream_t s, int count = 1, uint64_t in_stride = 0, uint64_t out_stride = 0);
+                   hipStream_t s, int count = 1, uint64_t in_stride = 0, uint64_t out_stride = 0,
+                   bool centre = false);
+// The whitener transforms its series less an integer offset c = rint(mean) and adds n c back to X_0: a float32
+// FFT rounds its partial sums at the ulp of the DC term (128 n for 8-bit trials, 10 sqrt(n) times the noise),
+// which the whitened spectrum showed at up to 5e-4 of the noise level in the bins with trivial twiddles.
+// x -= rint(stats[0]), the offset to cen[0] (stats: f32_stats' output)
+void f32_centre(float* x, uint64_t n, const float* stats, float* cen, hipStream_t s);
+// X[b * xstride].re += n c_b, c_b = cen[b], or (cen null) rint((float)(sum[b] / nvalid)) as the 8-bit sources take it
+void spectrum_add_dc(float2* X, uint64_t xstride, int count, uint64_t n, const unsigned long long* sum,
+                     uint64_t nvalid, const float* cen, hipStream_t s);
 void f32_stats(const float* x, uint64_t n, double* partials, int npartials, float* stats_out, hipStream_t s);
 
 // ----------------------------------------------------------------- spectra --
@@ -308,8 +317,8 @@ void fft4_pad_input(const float* in, uint64_t n, float* in_pad, const Fft4Geom& 
                     uint64_t in_stride = 0);
 // The same padded copy straight from 8-bit dedispersed rows (strip layouts
 // only: fft4_strip_layout(g), or a direct-source geometry's strips_direct): sample i < nvalid is in[i], then
-// the row mean (sum[b] / nvalid) up to n, zeros beyond -- u8_to_f32_pad and
-// fft4_pad_input in one pass.  count rows at in + b * in_stride.
+// the row mean (sum[b] / nvalid) up to n, zeros beyond -- u8_to_f32_pad (centre = true: every value less
+// rint(mean), as pass A's own 8-bit source) and fft4_pad_input in one pass.  count rows at in + b * in_stride.
 void fft4_pad_input_u8(const uint8_t* in, uint64_t nvalid, uint64_t n, const unsigned long long* sum, float* in_pad,
                        const Fft4Geom& g, hipStream_t s, int count, uint64_t in_stride);
 // Pass A: Y[k][k2][i] = W_M^{i k2} sum_j z_k[n1 j + i] W_n2^{j k2}, where

@@ -61,6 +61,16 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
+// An 8-bit row's mean as the whitener pads with it, and the integer offset its centred sources take off every
+// value before the transform (kernels.hpp f32_centre): one definition, so that every source and the kernel that
+// adds n * offset back to X_0 agree bit for bit.
+__device__ __forceinline__ float u8_mean(unsigned long long sum, uint64_t nvalid) {
+  return nvalid ? static_cast<float>(static_cast<double>(sum) / static_cast<double>(nvalid)) : 0.f;
+}
+__device__ __forceinline__ float u8_centre(unsigned long long sum, uint64_t nvalid) {
+  return rintf(u8_mean(sum, nvalid));
+}
+
 // Block-wide sum; `scratch` must hold blockDim.x/64 elements. Result valid
 // in every thread.
 template <class T>

@@ -453,8 +453,8 @@ __global__ void __launch_bounds__(256) fft4_strips_u8_kernel(const uint8_t* __re
   in += blockIdx.y * in_stride;
   out += blockIdx.y * out_stride;
   const uint32_t R = 1u << log2_r, pitch = rowlen + 16, j0 = blockIdx.x * R;
-  const float mean = nvalid ? static_cast<float>(static_cast<double>(sum[blockIdx.y]) / static_cast<double>(nvalid))
-                            : 0.f;
+  // centred (u8_to_f32_pad, centre = true)
+  const float cen = dev::u8_centre(sum[blockIdx.y], nvalid), mean = dev::u8_mean(sum[blockIdx.y], nvalid) - cen;
   // stage rows j0 .. j0 + R - 1 whole and the first 16 bytes of row j0 + R
   const uint32_t c16 = rowlen >> 4, nchunks = R * c16 + 1;
   for (uint32_t i = threadIdx.x; i < nchunks; i += blockDim.x) {
@@ -482,11 +482,12 @@ __global__ void __launch_bounds__(256) fft4_strips_u8_kernel(const uint8_t* __re
     float x[kStripW];
     if (s0 + kStripW <= nvalid) {
 #pragma unroll
-      for (int e = 0; e < kStripW; ++e) x[e] = static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u);
+      for (int e = 0; e < kStripW; ++e) x[e] = static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u) - cen;
     } else {
 #pragma unroll
       for (int e = 0; e < kStripW; ++e)
-        x[e] = s0 + e < nvalid ? static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u) : (s0 + e < n ? mean : 0.f);
+        x[e] = s0 + e < nvalid ? static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u) - cen
+                               : (s0 + e < n ? mean : 0.f);
     }
     store_strip_row(out + (static_cast<uint64_t>(b) * nrows + j0 + jj) * kStripW, x);
   }
@@ -582,8 +583,8 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, Cfg<L, CPT, SUB>::
     static_assert(CPT == 8 || CPT == 4, "8-bit rows: 16- or 8-byte loads");
     const uint8_t* row = g.u8 + src * g.src_stride;
     const uint64_t nvalid = g.u8_nvalid;
-    const float mean = nvalid ? static_cast<float>(static_cast<double>(g.u8sum[src]) / static_cast<double>(nvalid))
-                              : 0.f;
+    // centred (u8_to_f32_pad, centre = true)
+    const float cen = dev::u8_centre(g.u8sum[src], nvalid), mean = dev::u8_mean(g.u8sum[src], nvalid) - cen;
 #pragma unroll
     for (int q = 0; q < kPts; ++q) {
       const uint64_t s0 = 2 * (static_cast<uint64_t>(N1) * (t + q * T) + c0);
@@ -598,10 +599,11 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, Cfg<L, CPT, SUB>::
           wd[0] = w.x, wd[1] = w.y;
         }
 #pragma unroll
-        for (int e = 0; e < 2 * CPT; ++e) x[e] = static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u);
+        for (int e = 0; e < 2 * CPT; ++e) x[e] = static_cast<float>((wd[e >> 2] >> (8 * (e & 3))) & 255u) - cen;
       } else {
 #pragma unroll
-        for (int e = 0; e < 2 * CPT; ++e) x[e] = s0 + e < nvalid ? static_cast<float>(row[s0 + e]) : (s0 + e < n ? mean : 0.f);
+        for (int e = 0; e < 2 * CPT; ++e)
+          x[e] = s0 + e < nvalid ? static_cast<float>(row[s0 + e]) - cen : (s0 + e < n ? mean : 0.f);
       }
 #pragma unroll
       for (int c = 0; c < CPT; ++c) v[c][q] = make_float2(x[2 * c], x[2 * c + 1]);

@@ -96,6 +96,9 @@ __global__ void median_small_kernel(const float* __restrict__ in, int count, flo
 // linear_stretch_functor (kernels.cu:983-999) evaluated at output index i
 __device__ __forceinline__ float stretch_at(const float* __restrict__ in, uint64_t in_count, float step,
                                             uint64_t i) {
+  // the product rounded to float, as the reference's functor defines it: contracted into the subtraction below
+  // (fma(i, step, -j)) frac differs by up to half an ulp of x, 3e-4 of the median at bin 5e5 of a 2^20 spectrum
+#pragma clang fp contract(off)
   float x = static_cast<float>(static_cast<unsigned>(i)) * step;
   unsigned j = static_cast<unsigned>(x);
   if (j >= in_count) j = static_cast<unsigned>(in_count - 1);

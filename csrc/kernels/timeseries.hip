@@ -44,11 +44,13 @@ __global__ void __launch_bounds__(256) u8_sum_kernel(const uint8_t* __restrict__
 __global__ void __launch_bounds__(256) u8_to_f32_pad_kernel(const uint8_t* __restrict__ in, uint64_t nvalid,
                                                             float* __restrict__ out, uint64_t n,
                                                             const unsigned long long* __restrict__ sum,
-                                                            uint64_t in_stride, uint64_t out_stride) {
+                                                            uint64_t in_stride, uint64_t out_stride, bool centre) {
   in += blockIdx.y * in_stride;
   out += blockIdx.y * out_stride;
   sum += blockIdx.y;
-  const float mean = nvalid ? static_cast<float>(static_cast<double>(*sum) / static_cast<double>(nvalid)) : 0.f;
+  // centre: every value less rint(mean), exactly (integers; the pad by Sterbenz' lemma)
+  const float cen = centre ? dev::u8_centre(*sum, nvalid) : 0.f;
+  const float mean = dev::u8_mean(*sum, nvalid) - cen;
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
   // 4 samples per thread per step
   const uint64_t n4 = n / 4;
@@ -58,22 +60,42 @@ __global__ void __launch_bounds__(256) u8_to_f32_pad_kernel(const uint8_t* __res
     float4 r;
     if (i + 4 <= nvalid && aligned4) {
       const uchar4 b = *reinterpret_cast<const uchar4*>(in + i);  // one dword load
-      r = make_float4(b.x, b.y, b.z, b.w);
+      r = make_float4(b.x - cen, b.y - cen, b.z - cen, b.w - cen);
     } else if (i + 4 <= nvalid) {
-      r.x = in[i];
-      r.y = in[i + 1];
-      r.z = in[i + 2];
-      r.w = in[i + 3];
+      r.x = in[i] - cen;
+      r.y = in[i + 1] - cen;
+      r.z = in[i + 2] - cen;
+      r.w = in[i + 3] - cen;
     } else {
-      r.x = (i < nvalid) ? static_cast<float>(in[i]) : mean;
-      r.y = (i + 1 < nvalid) ? static_cast<float>(in[i + 1]) : mean;
-      r.z = (i + 2 < nvalid) ? static_cast<float>(in[i + 2]) : mean;
-      r.w = (i + 3 < nvalid) ? static_cast<float>(in[i + 3]) : mean;
+      r.x = (i < nvalid) ? static_cast<float>(in[i]) - cen : mean;
+      r.y = (i + 1 < nvalid) ? static_cast<float>(in[i + 1]) - cen : mean;
+      r.z = (i + 2 < nvalid) ? static_cast<float>(in[i + 2]) - cen : mean;
+      r.w = (i + 3 < nvalid) ? static_cast<float>(in[i + 3]) - cen : mean;
     }
     reinterpret_cast<float4*>(out)[v] = r;
   }
   for (uint64_t i = n4 * 4 + blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < n; i += stride)
-    out[i] = i < nvalid ? static_cast<float>(in[i]) : mean;
+    out[i] = i < nvalid ? static_cast<float>(in[i]) - cen : mean;
+}
+
+// x -= rint(stats[0]) (the series' mean); the offset goes to cen[0]
+__global__ void __launch_bounds__(256) f32_centre_kernel(float* __restrict__ x, uint64_t n,
+                                                         const float* __restrict__ stats, float* __restrict__ cen) {
+  const float c = rintf(stats[0]);
+  if (blockIdx.x == 0 && threadIdx.x == 0) cen[0] = c;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) x[i] -= c;
+}
+
+// bin 0 of spectrum b gets back the offset its series was centred by: X_0 += n c
+__global__ void spectrum_add_dc_kernel(float2* __restrict__ X, uint64_t xstride, int count, double n,
+                                       const unsigned long long* __restrict__ sum, uint64_t nvalid,
+                                       const float* __restrict__ cen) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= count) return;
+  const float c = cen ? cen[b] : dev::u8_centre(sum[b], nvalid);
+  float2* x0 = X + static_cast<uint64_t>(b) * xstride;
+  x0->x = static_cast<float>(static_cast<double>(x0->x) + n * static_cast<double>(c));  // n c is exact in double
 }
 
 // Partial sums of x and x^2 (double) -> partials[2*block]
@@ -135,12 +157,24 @@ void u8_sum(const uint8_t* in, uint64_t n, unsigned long long* sum, hipStream_t 
 }
 
 void u8_to_f32_pad(const uint8_t* in, uint64_t nvalid, float* out, uint64_t n, const unsigned long long* sum,
-                   hipStream_t s, int count, uint64_t in_stride, uint64_t out_stride) {
+                   hipStream_t s, int count, uint64_t in_stride, uint64_t out_stride, bool centre) {
   PSOUP_CHECK((reinterpret_cast<uintptr_t>(out) & 15) == 0 && out_stride % 4 == 0, "output must be 16-byte aligned");
   PSOUP_CHECK(count >= 1 && count <= 65535, "u8_to_f32_pad: bad count");
   const dim3 grid(dev::grid_for(n / 4 + 1, 256, count > 1 ? 1024 : 2048), static_cast<unsigned>(count));
-  u8_to_f32_pad_kernel<<<grid, 256, 0, s>>>(in, nvalid, out, n, sum, in_stride, out_stride);
+  u8_to_f32_pad_kernel<<<grid, 256, 0, s>>>(in, nvalid, out, n, sum, in_stride, out_stride, centre);
   post_launch_check("u8_to_f32_pad_kernel", s);
+}
+
+void f32_centre(float* x, uint64_t n, const float* stats, float* cen, hipStream_t s) {
+  f32_centre_kernel<<<dev::grid_for(n, 256, 2048), 256, 0, s>>>(x, n, stats, cen);
+  post_launch_check("f32_centre_kernel", s);
+}
+
+void spectrum_add_dc(float2* X, uint64_t xstride, int count, uint64_t n, const unsigned long long* sum,
+                     uint64_t nvalid, const float* cen, hipStream_t s) {
+  PSOUP_CHECK(count >= 1 && (sum || cen), "spectrum_add_dc: bad arguments");
+  spectrum_add_dc_kernel<<<(count + 63) / 64, 64, 0, s>>>(X, xstride, count, static_cast<double>(n), sum, nvalid, cen);
+  post_launch_check("spectrum_add_dc_kernel", s);
 }
 
 void f32_stats(const float* x, uint64_t n, double* partials, int npartials, float* stats_out, hipStream_t s) {

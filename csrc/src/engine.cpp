@@ -593,6 +593,7 @@ Whitener::Whitener(uint64_t n, float tsamp, hipStream_t stream, bool allow_fft4)
   m125_.resize(std::max<uint64_t>(1, nb / 5 / 5 / 5));
   partials_.resize(2 * 1024);
   stats_.resize(4);
+  cstat_.resize(4);
   sum_.resize(1);
   if (f4_) {
     auto tab = kern::fft4_tables(g4_);
@@ -685,10 +686,24 @@ void Whitener::inverse(const float2* d_spec, float* d_series) {
   kern::fft4_c2r_post(x4_.data(), M, kern::xlayout_args(g4_, kern::fft4_x_layout(g4_)), d_series, stream_);
 }
 
-void Whitener::load_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series) {
+void Whitener::load_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series, bool centre) {
   const uint64_t nvalid = std::min(nsamps, n_);
   kern::u8_sum(d_trial, nvalid, sum_.data(), stream_);
-  kern::u8_to_f32_pad(d_trial, nvalid, d_series, n_, sum_.data(), stream_);
+  kern::u8_to_f32_pad(d_trial, nvalid, d_series, n_, sum_.data(), stream_, 1, 0, 0, centre);
+  loaded_nvalid_ = nvalid;
+}
+
+void Whitener::restore_dc(float2* d_spec) {
+  kern::spectrum_add_dc(d_spec, nbins(), 1, n_, sum_.data(), loaded_nvalid_, nullptr, stream_);
+}
+
+void Whitener::whiten_trial(const uint8_t* d_trial, uint64_t nsamps, float* d_series, const uint32_t* d_zapmask,
+                            float* d_stats, float boundary5, float boundary25) {
+  load_trial(d_trial, nsamps, d_series, true);
+  forward(d_series, fser_.data());
+  restore_dc(fser_.data());
+  dered_stats(fser_.data(), d_zapmask, d_stats, boundary5, boundary25);
+  inverse(fser_.data(), d_series);
 }
 
 void Whitener::dered_stats(float2* spec, const uint32_t* d_zapmask, float* d_stats, float boundary5,
@@ -706,8 +721,14 @@ void Whitener::dered_stats(float2* spec, const uint32_t* d_zapmask, float* d_sta
 }
 
 void Whitener::whiten(float* d_series, const uint32_t* d_zapmask, bool with_stats, float boundary5, float boundary25) {
+  float* d_stats = with_stats ? stats_.data() : nullptr;
+  // a float series of unknown origin: its mean measured first.  Transformed less rint(mean), X_0 restored
+  // (kernels.hpp f32_centre): a series whose mean rounds to 0 is untouched
+  kern::f32_stats(d_series, n_, partials_.data(), 1024, cstat_.data(), stream_);
+  kern::f32_centre(d_series, n_, cstat_.data(), cstat_.data() + 3, stream_);
   forward(d_series, fser_.data());
-  dered_stats(fser_.data(), d_zapmask, with_stats ? stats_.data() : nullptr, boundary5, boundary25);
+  kern::spectrum_add_dc(fser_.data(), nbins(), 1, n_, nullptr, 0, cstat_.data() + 3, stream_);
+  dered_stats(fser_.data(), d_zapmask, d_stats, boundary5, boundary25);
   inverse(fser_.data(), d_series);
 }
 
@@ -747,10 +768,8 @@ bool Whitener::whiten_batch(const uint8_t* d_trials, uint64_t row_stride, uint64
   if (!f4_) {
     for (int b = 0; b < count; ++b) {
       float* x = d_out + static_cast<uint64_t>(b) * out_stride;
-      load_trial(d_trials + static_cast<uint64_t>(b) * row_stride, nsamps, x);
-      forward(x, fser_.data());
-      dered_stats(fser_.data(), d_zapmask, d_stats + 4 * b, boundary5, boundary25);
-      inverse(fser_.data(), x);
+      whiten_trial(d_trials + static_cast<uint64_t>(b) * row_stride, nsamps, x, d_zapmask, d_stats + 4 * b, boundary5,
+                   boundary25);
     }
     return false;
   }
@@ -778,17 +797,18 @@ bool Whitener::whiten_batch(const uint8_t* d_trials, uint64_t row_stride, uint64
     g.strips_direct = true;
   } else if (direct && out_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {
     // pass A reads the f32 copy itself (no padded copy)
-    kern::u8_to_f32_pad(d_trials, nvalid, d_out, n_, bsum_.data(), stream_, count, row_stride, out_stride);
+    kern::u8_to_f32_pad(d_trials, nvalid, d_out, n_, bsum_.data(), stream_, count, row_stride, out_stride, true);
     g.f32_direct = true;
   } else if (kern::fft4_strip_layout(g4_) && u8_aligned) {
     kern::fft4_pad_input_u8(d_trials, nvalid, n_, bsum_.data(), in4_.data(), g4_, stream_, count, row_stride);
   } else {
-    kern::u8_to_f32_pad(d_trials, nvalid, d_out, n_, bsum_.data(), stream_, count, row_stride, out_stride);
+    kern::u8_to_f32_pad(d_trials, nvalid, d_out, n_, bsum_.data(), stream_, count, row_stride, out_stride, true);
     kern::fft4_pad_input(d_out, n_, in4_.data(), g4_, stream_, count, out_stride);
   }
   kern::fft4_resample_colpass(d_out, in4_.data(), n_, af0_.data(), count, y4_.data(), g, tab4_.data(), stream_);
   kern::fft4_rowpass(y4_.data(), x4_.data(), count, g4_, tab4_.data(), stream_);
   kern::fft4_r2c_half(x4_.data(), M, L, bspec_.data(), stream_, count, g4_.xstride, nb);
+  kern::spectrum_add_dc(bspec_.data(), nb, count, n_, bsum_.data(), nvalid, nullptr, stream_);  // every source is centred
   {
     // running median, dereddening + zapping and interbin stats of all items
     const uint64_t n5 = nb / 5, n25 = n5 / 5, n125 = n25 / 5, ms = std::max<uint64_t>(1, n5);
@@ -1826,8 +1846,7 @@ FoldEngine::FoldEngine(uint64_t nsamps, float tsamp, hipStream_t stream) : n_(ns
 
 std::vector<FoldResult> FoldEngine::fold_trial(const uint8_t* d_trial, uint64_t trial_nsamps,
                                                const std::vector<double>& periods, const std::vector<float>& accs) {
-  wh_->load_trial(d_trial, trial_nsamps, tim_.data());
-  wh_->whiten(tim_.data(), nullptr, false, 0.05f, 0.5f);
+  wh_->whiten_trial(d_trial, trial_nsamps, tim_.data(), nullptr, nullptr, 0.05f, 0.5f);
   return fold_series(tim_.data(), periods, accs);
 }
 
@@ -1977,10 +1996,11 @@ void coincidencer_beam(const uint8_t* d_trial, uint64_t n, float tsamp, BeamProd
   Whitener wh(n, tsamp, stream);
   out.series.resize(n);
   out.spectrum.resize(wh.nbins());
-  wh.load_trial(d_trial, n, out.series.data());
+  wh.load_trial(d_trial, n, out.series.data(), true);  // centred: X_0 restored below
   // whiten without the C2R so the dereddened spectrum can be formed first
   const uint64_t nb = wh.nbins();
   wh.forward(out.series.data(), wh.spectrum());
+  wh.restore_dc(wh.spectrum());
   DeviceBuffer<float> m5(nb / 5), m25(std::max<uint64_t>(1, nb / 25)), m125(std::max<uint64_t>(1, nb / 125));
   const uint64_t n5 = nb / 5, n25 = n5 / 5, n125 = n25 / 5;
   kern::median5_amp(wh.spectrum(), nb, m5.data(), stream);

@@ -177,6 +177,101 @@ def whiten(trial_u8: np.ndarray, n: int, tsamp: float, zapmask=None, with_stats=
     return series, st
 
 
+# The whitener from its definition in float64.  The values are float64; the
+# integer decisions of the algorithm (the region switches, the zap ranges, the
+# stretch's node index and its interpolation guard) are taken in float32,
+# exactly as ``running_median`` / ``linear_stretch`` / ``zap_mask`` and the
+# kernels take them.
+def whiten_positions(n: int, tsamp: float, b5: float = 0.05, b25: float = 0.5):
+    """(bin_width as float32, pos5, pos25): the bins at which the running
+    median switches from the medians of 5 to those of 25 and of 125."""
+    bw = np.float32(1.0 / np.float32(np.float32(n) * np.float32(tsamp)))
+    return bw, int(np.float32(b5) / bw), int(np.float32(b25) / bw)
+
+
+def stretch_nodes(in_count: int, out_count: int):
+    """``linear_stretch``'s decisions per output bin: (j, frac, interpolate),
+    j the left node (int64), frac the float32 weight of node j + 1 (as
+    float64), interpolate = frac > 1e-5f and j + 1 < in_count."""
+    step = np.float32(in_count - 1) / np.float32(out_count - 1)
+    xi = np.arange(out_count, dtype=np.uint32).astype(np.float32) * step
+    j = np.minimum(xi.astype(np.uint32), in_count - 1).astype(np.int64)
+    frac = (xi - j.astype(np.float32)).astype(np.float32)
+    use = (frac > np.float32(1e-5)) & (j + 1 < in_count)
+    return j, frac.astype(np.float64), use
+
+
+def linear_stretch64(x: np.ndarray, out_count: int, nodes=None) -> np.ndarray:
+    """``linear_stretch`` with float64 values (nodes: ``stretch_nodes``'s
+    tuple, default the stretch's own)."""
+    x = np.asarray(x, dtype=np.float64)
+    j, frac, use = stretch_nodes(len(x), out_count) if nodes is None else nodes
+    a = x[j]
+    nxt = x[np.minimum(j + 1, len(x) - 1)]
+    return np.where(use, a + frac * (nxt - a), a)
+
+
+def median_scrunch5_64(x: np.ndarray) -> np.ndarray:
+    """``median_scrunch5`` in float64."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    if n < 5:
+        if n == 1:
+            return x[:1].copy()
+        if n == 2:
+            return np.array([0.5 * (x[0] + x[1])])
+        if n == 3:
+            return np.array([np.median(x)])
+        s = np.sort(x)
+        return np.array([0.5 * (s[1] + s[2])])
+    m = n // 5
+    return np.median(x[: 5 * m].reshape(m, 5), axis=1)
+
+
+def running_median64(amp: np.ndarray, pos5: int, pos25: int) -> np.ndarray:
+    """``running_median`` in float64 with the switches given as bins: bin k
+    takes the stretched medians of 125 if k >= pos25, else of 25 if
+    k >= pos5, else of 5."""
+    nb = len(amp)
+    m5 = median_scrunch5_64(amp)
+    m25 = median_scrunch5_64(m5)
+    m125 = median_scrunch5_64(m25)
+    k = np.arange(nb)
+    return np.where(k >= pos25, linear_stretch64(m125, nb),
+                    np.where(k >= pos5, linear_stretch64(m25, nb), linear_stretch64(m5, nb)))
+
+
+def convert_pad64(trial_u8: np.ndarray, n: int) -> np.ndarray:
+    """``convert_pad`` as float64: the pad is the kernels' own value, the
+    float32 rounding of double(sum) / nvalid."""
+    return convert_pad(trial_u8, n).astype(np.float64)
+
+
+def stats64(P: np.ndarray) -> Tuple[float, float, float]:
+    P = np.asarray(P, dtype=np.float64)
+    mean = float(P.mean())
+    rms = float(np.sqrt((P * P).mean()))
+    return mean, rms, float(np.sqrt(max(rms * rms - mean * mean, 0.0)))
+
+
+def whiten64(trial_u8: np.ndarray, n: int, tsamp: float, zap_freqs=(), zap_widths=(), b5: float = 0.05,
+             b25: float = 0.5):
+    """The whitener's dereddened half spectrum from its definition, float64:
+    the first min(nsamps, n) samples mean-padded to n -> real FFT -> divided
+    by the running median of |X| -> bins 0..4 zeroed -> zapped bins 1 + 0i
+    (zap wins over the zeroing).  Returns (D complex128 [n/2 + 1],
+    (mean, rms, std) of interbin64(D), pos5, pos25).  The whitened series is
+    irfft(D) * n."""
+    X = np.fft.rfft(convert_pad64(trial_u8, n))
+    nb = len(X)
+    bw, pos5, pos25 = whiten_positions(n, tsamp, b5, b25)
+    D = X / running_median64(np.abs(X), pos5, pos25)
+    D[:5] = 0
+    if len(zap_freqs):
+        D[zap_mask(zap_freqs, zap_widths, float(bw), nb)] = 1 + 0j
+    return D, stats64(interbin64(D)), pos5, pos25
+
+
 # ---------------------------------------------------------- acceleration ---
 def accel_factor(acc: float, tsamp: float) -> float:
     return (float(np.float32(acc)) * float(np.float32(tsamp))) / (2 * C_LIGHT)

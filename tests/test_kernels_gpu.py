@@ -288,7 +288,10 @@ def test_spectrum_forms_and_running_median():
 
 
 def test_whitening_engine_matches_reference(C):
-    """Whitener path of SearchEngine (convert/pad, R2C, median, deredden, zap, C2R)."""
+    """Whitener path of SearchEngine (convert/pad, R2C, median, deredden, zap, C2R) at the production tsamp with a
+    zap entry, against the float32 NumPy reference.  Measured (MI355X): series 8.07e-7 of max |series|, mean equal
+    to the last bit, std 1.04e-7 relative; the bounds are 4 x these, the mean's 4 float32 ulps (the per-bin
+    comparison with the float64 oracle is test_whiten_exact.py)."""
     rng = np.random.default_rng(11)
     nsamps, n = 100000, 1 << 17
     trial = rng.integers(60, 200, size=nsamps, dtype=np.uint8)
@@ -309,8 +312,10 @@ def test_whitening_engine_matches_reference(C):
     exp, st = ref.whiten(trial, n, 0.00032, zm)
     got = w.cpu().numpy()
     scale = np.abs(exp).max()
-    assert np.abs(got - exp).max() / scale < 2e-5
-    assert stt[0].item() == pytest.approx(st[0], rel=1e-4) and stt[2].item() == pytest.approx(st[2], rel=1e-3)
+    print(f"WHITEN_ENGINE series {np.abs(got - exp).max() / scale:.3e} mean {abs(stt[0].item() - st[0]) / st[0]:.3e} "
+          f"std {abs(stt[2].item() - st[2]) / st[2]:.3e}")
+    assert np.abs(got - exp).max() / scale < 3.2e-6
+    assert stt[0].item() == pytest.approx(st[0], rel=4 * 2.0 ** -23) and stt[2].item() == pytest.approx(st[2], rel=4.1e-7)
 
 
 def test_resample_batch_and_v1():
