@@ -211,7 +211,8 @@ struct SearchParams {
   // Acceleration-trial FFT path: 0 = rocFFT R2C of N points; 1 = rocFFT C2C
   // of N/2 points with the real-FFT post-processing fused into the interbin
   // kernel; 2 = resample fused into a two-pass four-step FFT (fft4step.hip,
-  // default; falls back to 1 when N/2 is not N1*N2 with N1,N2 in 128..4096).
+  // default; falls back to 1 when N/2 is not N1*N2 with N1,N2 in 128..4096, and
+  // 1 to 0 when N/2 is not a power of two).
   int fft_mode = 2;
 };
 

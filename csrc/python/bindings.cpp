@@ -1131,6 +1131,7 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("sub_batch", &SearchEngine::sub_batch)
       .def_property_readonly("fft_mode", &SearchEngine::fft_mode)
       .def_property_readonly("rows_ext", &SearchEngine::rows_ext)
+      .def_property_readonly("whiten_mixed_radix", [](const SearchEngine& e) { return e.whitener().mixed_radix(); })
       .def_property_readonly("stream", [](const SearchEngine& e) { return reinterpret_cast<uintptr_t>(e.stream()); })
       .def_property_readonly("tobs", &SearchEngine::tobs)
       .def_property_readonly("stats_address", [](const SearchEngine& e) { return reinterpret_cast<uintptr_t>(e.trial_stats()); })

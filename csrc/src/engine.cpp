@@ -916,6 +916,9 @@ SearchEngine::SearchEngine(const SearchParams& p, hipStream_t stream)
     rows_ext_ = f4_.ok;
   }
   if (mode_ == 2 && !f4_.ok) mode_ = 1;
+  // the fused r2c of mode 1 indexes its half-length transform by powers of
+  // two (r2c_interbin_normalise_batch): other even lengths take the N-point R2C
+  if (mode_ == 1 && ((n_ / 2) & (n_ / 2 - 1)) != 0) mode_ = 0;
   if (const char* pd = std::getenv("PSOUP_WHITEN_PAD_DIRECT")) pad_direct_ = std::atoi(pd) != 0;
   if (mode_ == 2) {
     auto tab = kern::fft4_tables(f4_);
@@ -940,7 +943,8 @@ SearchEngine::SearchEngine(const SearchParams& p, hipStream_t stream)
       bounds_.push_back(b);
       hp_.start[h] = b.start_idx;
       hp_.end[h] = std::max(b.start_idx, b.end_idx);
-      hi_ = std::max(hi_, hp_.end[h]);
+      // (an empty range -- min_freq beyond the level's last bin -- reads no bin: its start may lie past nb_)
+      if (b.end_idx > b.start_idx) hi_ = std::max(hi_, b.end_idx);
     } else {
       hp_.start[h] = hp_.end[h] = 0;
     }

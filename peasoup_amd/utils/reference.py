@@ -347,23 +347,213 @@ def unique_peaks(idxs: np.ndarray, snrs: np.ndarray, min_gap: int = 30):
     return out
 
 
-def spectrum_peaks(series: np.ndarray, af: float, mean: float, std: float, n: int, bin_width: float,
-                   nharm: int, thresh: float, min_freq: float, max_freq: float):
-    """One acceleration trial: resample, R2C, interbin, normalise, harmonic sums,
-    peaks -> list of (nh, idx, snr, freq)."""
-    r = resample_ii(series, af)
-    X = np.fft.rfft(r.astype(np.float64)).astype(np.complex64)
-    P = interbin(X)
-    P = ((P - np.float32(np.float32(mean) * np.float32(n))) / np.float32(np.float32(std) * np.float32(n))).astype(np.float32)
-    levels = [P] + harmonic_sums(P, nharm)
-    res = []
-    for h, L in enumerate(levels):
-        s, e, fac = peak_bounds(len(P), bin_width, h, min_freq, max_freq)
-        seg = L[s:e]
-        idx = np.nonzero(seg > np.float32(thresh))[0] + s
-        for pi, ps in unique_peaks(idx, L[idx]):
-            res.append((h, pi, ps, float(np.float32(pi * fac))))
-    return res
+# -------------------------------------------- the search of one DM trial ----
+# Float64 oracle of SearchEngine::search_trial, written from the definition of
+# the search: whiten64 -> search_spectrum per acceleration -> harmonic sums ->
+# crossings inside peak_bounds -> unique_peaks -> candidates -> the per-trial
+# harmonic distiller -> the per-DM acceleration distiller.  The values are
+# float64; the integer and float32 decisions (tobs, bin_width, the search
+# ranges, the threshold, the candidate frequency, the distillers' tolerances)
+# are taken in float32 where the engine takes them.
+class Cand:
+    """A candidate of the Python distillers (the fields of psoup::Candidate)."""
+
+    def __init__(self, dm, dm_idx, acc, nh, snr, freq):
+        self.dm, self.dm_idx, self.acc, self.nh, self.snr, self.freq = dm, dm_idx, acc, nh, snr, freq
+        self.assoc = []
+
+
+def f32(x):
+    return float(np.float32(x))
+
+
+def py_distill(cands, cond):
+    """BaseDistiller::distill (distiller.hpp): sort by descending S/N, then
+    every still-unique candidate in turn marks the later ones related to it."""
+    cands = sorted(cands, key=lambda c: -c.snr)
+    uniq = [True] * len(cands)
+    start = 0
+    while True:
+        idx = -1
+        for ii in range(start, len(cands)):
+            if uniq[ii]:
+                start, idx = ii + 1, ii
+                break
+        if idx < 0:
+            break
+        cond(cands, idx, uniq)
+    return [c for c, u in zip(cands, uniq) if u]
+
+
+def harm_related(f0, freqs, nhs, tol, max_harm, frac):
+    """HarmonicDistiller::condition: per later candidate (freqs, nhs) the
+    number of (jj, kk), jj = 1..max_harm, kk = 1..(2^nh if frac else 1), with
+    1 - tol < kk f / (jj f0) < 1 + tol (tol as float32, the ratio in double)."""
+    f = np.asarray(freqs, dtype=np.float64)
+    maxd = np.array([2.0 ** h if frac else 1.0 for h in nhs], dtype=np.float64)
+    if not len(f):
+        return np.zeros(0, dtype=np.int64)
+    jj = np.arange(1, int(max_harm) + 1, dtype=np.float64)
+    kk = np.arange(1, int(maxd.max()) + 1, dtype=np.float64)
+    r = (kk[None, None, :] * f[:, None, None]) / (jj[None, :, None] * f0)
+    hit = (r > 1 - f32(tol)) & (r < 1 + f32(tol)) & (kk[None, None, :] <= maxd[:, None, None])
+    return hit.sum(axis=(1, 2))
+
+
+def harm_cond(tol, max_harm, keep, frac):
+    def cond(c, idx, uniq):
+        rest = c[idx + 1:]
+        n = harm_related(c[idx].freq, [x.freq for x in rest], [x.nh for x in rest], tol, max_harm, frac)
+        for ii in np.nonzero(n)[0]:
+            if keep:  # once per matching (jj, kk)
+                c[idx].assoc.extend([rest[ii]] * int(n[ii]))
+            uniq[idx + 1 + ii] = False
+    return cond
+
+
+def acc_related(f0, a0, f, a, tobs, tol):
+    """AccelerationDistiller::condition: is (f, a) inside the window that the
+    fundamental (f0, a0) sweeps to at acceleration a, widened by f0 tol."""
+    edge = f0 * f32(tol)
+    af = f32(f0 + (a0 - a) * f0 * (f32(tobs) / C_LIGHT))
+    return (f0 - edge < f < af + edge) if af > f0 else (af - edge < f < f0 + edge)
+
+
+def acc_cond(tobs, tol, keep):
+    def cond(c, idx, uniq):
+        f0, a0 = c[idx].freq, c[idx].acc
+        for ii in range(idx + 1, len(c)):
+            if acc_related(f0, a0, c[ii].freq, c[ii].acc, tobs, tol):
+                if keep:
+                    c[idx].assoc.append(c[ii])
+                uniq[ii] = False
+    return cond
+
+
+def harmonic_levels64(P: np.ndarray, nlevels: int, scales=None, rounding: bool = True) -> List[np.ndarray]:
+    """Levels 0..nlevels of the incoherent harmonic sum in float64, every bin:
+    level h at bin i is 2^(-h/2) sum_{m = 1..2^h} P[(i m + 2^(h-1)) >> h]
+    (the nearest bin to i m / 2^h, ties up).  scales: the factor per level
+    (default LEVEL_SCALE); rounding False drops the 2^(h-1)."""
+    P = np.asarray(P, dtype=np.float64)
+    scales = LEVEL_SCALE if scales is None else scales
+    i = np.arange(len(P), dtype=np.int64)
+    out = [P * scales[0]]
+    for h in range(1, nlevels + 1):
+        r = (1 << (h - 1)) if rounding else 0
+        val = np.zeros(len(P))
+        for m in range(1, (1 << h) + 1):
+            val += P[(i * m + r) >> h]
+        out.append(val * scales[h])
+    return out
+
+
+def search_setup(params) -> Dict:
+    """What SearchEngine's constructor derives from its SearchParams: n, nb,
+    tobs and bin_width (float32, formed as the constructor forms them),
+    nlevels and per level the (start, end, factor) of the search range, end
+    not below start."""
+    n = int(params.fft_size)
+    nb = n // 2 + 1
+    tobs = np.float32(np.float32(n) * np.float32(params.tsamp))
+    bw = np.float32(1.0 / float(tobs))
+    nlev = min(max(int(params.nharmonics), 0), 5)
+    bounds = []
+    for h in range(nlev + 1):
+        s, e, fac = peak_bounds(nb, float(bw), h, params.min_freq, params.max_freq)
+        bounds.append((s, max(s, e), fac))
+    return dict(n=n, nb=nb, tobs=float(tobs), bin_width=float(bw), nlevels=nlev, bounds=bounds)
+
+
+def search_levels64(trial_u8: np.ndarray, nsamps: int, params, accs, floor: float, bounds=None, stats=None,
+                    search_accs=None, scales=None, rounding: bool = True) -> Dict:
+    """The dense part of the oracle: per acceleration trial and level, the
+    bins (ascending) inside the level's search range whose float64 value
+    exceeds ``floor``, and those values.
+
+    The whitened series is n irfft(D) of whiten64's D, the normalisation its
+    interbin (mean, std) times n: the engine's series is the unnormalised
+    inverse transform, and SpecOut::nscale = n scales the unit-scale stats to
+    it.  The keyword arguments exist for defective oracles: bounds replaces
+    search_setup's, stats = (mean, std) the trial's own, search_accs the
+    accelerations the spectra are formed at (the candidates keep accs)."""
+    su = search_setup(params)
+    n = su["n"]
+    if bounds is not None:
+        su["bounds"] = list(bounds)
+    tsamp = f32(params.tsamp)
+    D, st, _, _ = whiten64(np.asarray(trial_u8)[:nsamps], n, tsamp, list(params.zap_freqs), list(params.zap_widths),
+                           params.boundary_5_freq, params.boundary_25_freq)
+    x = np.fft.irfft(D, n) * n
+    mean, std = (st[0], st[2]) if stats is None else stats
+    trials = []
+    for a in (accs if search_accs is None else search_accs):
+        P = search_spectrum(x, a, tsamp, mean * n, std * n)
+        rows = []
+        for h, L in enumerate(harmonic_levels64(P, su["nlevels"], scales, rounding)):
+            s, e, _ = su["bounds"][h]
+            idx = np.nonzero(L[s:e] > floor)[0] + s
+            rows.append((idx, L[idx]))
+        trials.append(rows)
+    su.update(accs=[f32(a) for a in accs], floor=float(floor), trials=trials, stats=(mean, st[1], std))
+    return su
+
+
+def cluster_peaks64(idx: np.ndarray, val: np.ndarray, min_gap: int):
+    """unique_peaks with the evidence a test of it needs: per cluster (peak
+    bin, peak value, largest other value or -inf, number of crossings)."""
+    out = []
+    ii, n = 0, len(idx)
+    while ii < n:
+        first = ii
+        cpeak, cidx, last = val[ii], idx[ii], idx[ii]
+        ii += 1
+        while ii < n and idx[ii] - last < min_gap:
+            if val[ii] > cpeak:
+                cpeak, cidx, last = val[ii], idx[ii], idx[ii]
+            ii += 1
+        rest = np.sort(val[first:ii])[:-1]
+        out.append((int(cidx), float(cpeak), float(rest[-1]) if len(rest) else -np.inf, ii - first))
+    return out
+
+
+def search_candidates64(levels: Dict, params, min_snr: float, dm: float, dm_idx: int, raw: bool = False,
+                        min_gap: Optional[int] = None) -> Dict:
+    """The decisions of the oracle on search_levels64's values: crossings
+    strictly above float32(min_snr) (not below levels['floor']), clusters,
+    candidates (dm, dm_idx, acc, nh, snr, float32(bin factor)), the per-trial
+    harmonic distiller (freq_tol, max_harm, fractional, nothing kept) and,
+    unless raw, the per-DM acceleration distiller (tobs, freq_tol, related
+    ones kept).  Returns dict(cands, per_trial = the harmonic-distilled list
+    of every trial, harm_in = the lists before it, clusters[trial][level] =
+    cluster_peaks64's tuples)."""
+    thresh = f32(min_snr)
+    assert thresh >= levels["floor"], "the levels were not kept down to this threshold"
+    gap = int(params.min_gap) if min_gap is None else int(min_gap)
+    harm = harm_cond(params.freq_tol, f32(params.max_harm), False, True)
+    clusters, harm_in, per_trial = [], [], []
+    for acc, rows in zip(levels["accs"], levels["trials"]):
+        cl, trial = [], []
+        for h, (idx, val) in enumerate(rows):
+            keep = val > thresh
+            cl.append(cluster_peaks64(idx[keep], val[keep], gap))
+            fac = levels["bounds"][h][2]
+            trial += [Cand(f32(dm), int(dm_idx), acc, h, snr, f32(pi * fac)) for pi, snr, _, _ in cl[-1]]
+        clusters.append(cl)
+        harm_in.append(trial)
+        per_trial.append(py_distill(trial, harm))
+    cands = [c for t in per_trial for c in t]
+    if not raw:
+        cands = py_distill(cands, acc_cond(levels["tobs"], params.freq_tol, True))
+    return dict(cands=cands, per_trial=per_trial, harm_in=harm_in, clusters=clusters, min_snr=thresh)
+
+
+def search_trial64(trial_u8: np.ndarray, nsamps: int, params, accs, dm: float, dm_idx: int, raw: bool = False,
+                   **variant) -> Dict:
+    """SearchEngine::search_trial from its definition (search_levels64 at
+    floor = min_snr, then search_candidates64)."""
+    levels = search_levels64(trial_u8, nsamps, params, accs, f32(params.min_snr), **variant)
+    return search_candidates64(levels, params, params.min_snr, dm, dm_idx, raw)
 
 
 # ---------------------------------------------------------------- folding --

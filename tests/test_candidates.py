@@ -6,66 +6,7 @@ import numpy as np
 import pytest
 
 from peasoup_amd.utils import reference as ref
-
-
-class Cand:
-    def __init__(self, dm, dm_idx, acc, nh, snr, freq):
-        self.dm, self.dm_idx, self.acc, self.nh, self.snr, self.freq = dm, dm_idx, acc, nh, snr, freq
-        self.assoc = []
-
-
-def py_distill(cands, cond):
-    cands = sorted(cands, key=lambda c: -c.snr)
-    uniq = [True] * len(cands)
-    start = 0
-    while True:
-        idx = -1
-        for ii in range(start, len(cands)):
-            if uniq[ii]:
-                start, idx = ii + 1, ii
-                break
-        if idx < 0:
-            break
-        cond(cands, idx, uniq)
-    return [c for c, u in zip(cands, uniq) if u]
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-def harm_cond(tol, max_harm, keep, frac):
-    def cond(c, idx, uniq):
-        f0 = c[idx].freq
-        for ii in range(idx + 1, len(c)):
-            maxd = 2.0 ** c[ii].nh if frac else 1
-            for jj in range(1, int(max_harm) + 1):
-                kk = 1
-                while kk <= maxd:
-                    r = kk * c[ii].freq / (jj * f0)
-                    if 1 - f32(tol) < r < 1 + f32(tol):
-                        if keep:
-                            c[idx].assoc.append(c[ii])
-                        uniq[ii] = False
-                    kk += 1
-    return cond
-
-
-def acc_cond(tobs, tol, keep):
-    toc = f32(tobs) / 299792458.0
-
-    def cond(c, idx, uniq):
-        f0, a0 = c[idx].freq, c[idx].acc
-        edge = f0 * f32(tol)
-        for ii in range(idx + 1, len(c)):
-            af = f32(f0 + (a0 - c[ii].acc) * f0 * toc)
-            f = c[ii].freq
-            rel = (f0 - edge < f < af + edge) if af > f0 else (af - edge < f < f0 + edge)
-            if rel:
-                if keep:
-                    c[idx].assoc.append(c[ii])
-                uniq[ii] = False
-    return cond
+from peasoup_amd.utils.reference import Cand, acc_cond, f32, harm_cond, py_distill  # noqa: F401
 
 
 def dm_cond(tol, keep):

@@ -912,7 +912,9 @@ def test_whitening_into_padded_input_equals_pad_kernel(C, monkeypatch, log2n):
 def test_flat_multi_dm_batches_match_per_dm_search(C):
     """search_prepared_many: the trials of several DMs concatenated and cut
     into K-trial batches across DM boundaries (per-trial series index and
-    whitening stats) give each DM exactly the candidates of its own search."""
+    whitening stats) give each DM exactly the candidates of its own search.
+    (The engine against itself; test_search_engine_exact.py compares the flat
+    list with the search's definition in float64.)"""
     rng = np.random.default_rng(9)
     n, nsamps, count = 1 << 18, (1 << 18) + 300, 5
     rs = 1 << 19
