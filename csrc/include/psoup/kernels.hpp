@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace psoup {
@@ -154,6 +155,14 @@ void dedisperse_lds(const int8_t* chan_major, uint64_t chan_stride, const int32_
                     const int32_t* d_offT, int ldo, int d_base, int ndm, const int32_t* d_wmin, int max_window,
                     uint64_t out_nsamps, uint8_t* out, uint64_t out_stride, float scale, int nbits, int bias,
                     hipStream_t s);
+
+// Launch trace of the dedispersion launchers above and pack2_rows (host only,
+// off by default): while on, each launch appends the tag of the kernel
+// instantiation it starts -- "direct", "mfma", "mfma_lds", "pack2",
+// "valu<dpt=4,wide=1,xor=1>", "lds<xor=0,passes=2,dpt=4,bytes=0>",
+// "2bit<dpw=2>" -- to a log; dedisp_trace_take returns the log and clears it.
+void dedisp_trace(bool on);
+std::vector<std::string> dedisp_trace_take();
 
 // ------------------------------------------------------------ time series ---
 // count > 1: rows b at in + b*in_stride, sums sum[b], outputs out + b*out_stride.

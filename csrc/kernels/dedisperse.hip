@@ -13,7 +13,10 @@
 //     shifted data (A: 32 samples x 32 (channel,shift) pairs) with a one-hot
 //     selection matrix (B: 32 (channel,shift) pairs x 32 DMs); see below.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
+#include <mutex>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -24,6 +27,38 @@ namespace psoup {
 namespace kern {
 
 namespace {
+
+// Launch trace (host only, off by default): while on, every launcher below
+// appends the tag of the kernel instantiation it launches, written next to
+// the <<<>>> it names; the tests read it to assert which variant ran.
+std::atomic<bool> g_trace_on{false};
+std::mutex g_trace_mutex;
+std::vector<std::string> g_trace_log;
+
+void trace_add(std::string tag) {
+  std::lock_guard<std::mutex> lock(g_trace_mutex);
+  g_trace_log.push_back(std::move(tag));
+}
+// one predictable branch per launch while tracing is off
+#define PSOUP_DEDISP_TRACE(tag) \
+  if (g_trace_on.load(std::memory_order_relaxed)) trace_add(tag)
+
+// tags of the templated kernels, built from the launch's own template arguments
+template <int DPT, bool WIDE, bool XOR>
+std::string valu_tag() {
+  return "valu<dpt=" + std::to_string(DPT) + ",wide=" + std::to_string(int(WIDE)) + ",xor=" +
+         std::to_string(int(XOR)) + ">";
+}
+template <bool XOR, int PASSES, int DPT, int CPB, bool BYTES>
+std::string lds_tag() {
+  static_assert(CPB == 1, "the tag names no channels-per-buffer argument");
+  return "lds<xor=" + std::to_string(int(XOR)) + ",passes=" + std::to_string(PASSES) + ",dpt=" + std::to_string(DPT) +
+         ",bytes=" + std::to_string(int(BYTES)) + ">";
+}
+template <int DPW>
+std::string twobit_tag() {
+  return "2bit<dpw=" + std::to_string(DPW) + ">";
+}
 
 __device__ __forceinline__ uint8_t scale_out(int sum, float scale) {
   float v = static_cast<float>(sum) * scale;
@@ -825,6 +860,15 @@ __global__ void __launch_bounds__(256) dedisperse_2bit_kernel(
 
 }  // namespace
 
+void dedisp_trace(bool on) { g_trace_on.store(on, std::memory_order_relaxed); }
+
+std::vector<std::string> dedisp_trace_take() {
+  std::lock_guard<std::mutex> lock(g_trace_mutex);
+  std::vector<std::string> log;
+  log.swap(g_trace_log);
+  return log;
+}
+
 void dedisperse_direct(const int8_t* chan_major, uint64_t chan_stride, int nchans, const int32_t* offsets,
                        const int32_t* killmask, int ndm, uint64_t out_nsamps, uint8_t* out, uint64_t out_stride,
                        float scale, int bias, int nactive, hipStream_t s) {
@@ -832,6 +876,7 @@ void dedisperse_direct(const int8_t* chan_major, uint64_t chan_stride, int nchan
   PSOUP_CHECK(ndm <= 65535, "too many DMs per launch");
   uint64_t gx = (out_nsamps + 1023) / 1024;
   dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(ndm));
+  PSOUP_DEDISP_TRACE("direct");
   dedisperse_direct_kernel<<<grid, 256, 0, s>>>(chan_major, chan_stride, nchans, offsets, killmask, out_nsamps,
                                                  out, out_stride, scale, bias * nactive);
   post_launch_check("dedisperse_direct_kernel", s);
@@ -913,6 +958,7 @@ void dedisperse_mfma(const int8_t* chan_major, uint64_t chan_stride, const int32
   PSOUP_CHECK(d_skip >= 0 && d_skip < 32 && d_skip + ndm <= 32 * ntiles, "dedisperse_mfma: bad tile range");
   const uint64_t ntt = (out_nsamps + kMfmaWgSamples - 1) / kMfmaWgSamples;
   dim3 grid(static_cast<unsigned>(ntiles), static_cast<unsigned>(std::min<uint64_t>(ntt, 65535)));
+  PSOUP_DEDISP_TRACE("mfma");
   dedisperse_mfma_kernel<<<grid, 256, 0, s>>>(chan_major, chan_stride, reinterpret_cast<const int4*>(d_steps),
                                                d_deltas, reinterpret_cast<const int2*>(d_tile_info), ndm, d_skip,
                                                out_nsamps,
@@ -934,9 +980,12 @@ void dedisperse_valu(const int8_t* chan_major, uint64_t chan_stride, const int32
   PSOUP_CHECK(ty <= 0x7FFFFFFF, "dedisperse_valu: series too long");
   dim3 grid(static_cast<unsigned>((ndm + 4 * dpt - 1) / (4 * dpt)), static_cast<unsigned>(ty));
   PSOUP_CHECK(d_base + static_cast<int>(grid.x) * 4 * dpt <= ldo, "dedisperse_valu: offset table too narrow");
-#define PSOUP_VALU_LAUNCH(D, W, X)                                                                            \
-  dedisperse_valu_kernel<D, W, X><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive, d_offT, ldo, \
-                                                       d_base, ndm, out_nsamps, out, out_stride, scale)
+#define PSOUP_VALU_LAUNCH(D, W, X)                                                                              \
+  do {                                                                                                          \
+    PSOUP_DEDISP_TRACE((valu_tag<D, W, X>()));                                                                  \
+    dedisperse_valu_kernel<D, W, X><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive, d_offT, ldo, \
+                                                         d_base, ndm, out_nsamps, out, out_stride, scale);       \
+  } while (0)
   if (wide) {
     if (bias == 128)
       PSOUP_VALU_LAUNCH(4, true, true);
@@ -1062,6 +1111,7 @@ void dedisperse_mfma_lds(const int8_t* chan_major, uint64_t chan_stride, const i
     return;
   }
   dim3 grid(static_cast<unsigned>(ntiles), static_cast<unsigned>(ty));
+  PSOUP_DEDISP_TRACE("mfma_lds");
   dedisperse_mfma_lds_kernel<kMfmaLdsGroup><<<grid, 256, 0, s>>>(
       chan_major, chan_stride, d_active, nactive, reinterpret_cast<const uint32_t*>(d_steps), d_relo,
       reinterpret_cast<const int2*>(d_ginfo), ngroups, d_wmin, ndm, d_skip, out_nsamps, out, out_stride, scale,
@@ -1108,31 +1158,29 @@ void dedisperse_lds(const int8_t* chan_major, uint64_t chan_stride, const int32_
   const int max_raw = (1 << std::min(nbits, 8)) - 1;
   const int flush = max_raw > 0 ? 255 / max_raw : 255;
   const bool bytes = !xr && nbits <= 4 && flush >= 1 && !two;
+  // (F: the byte lanes' spill cadence; 255 where the kernel has none)
+#define PSOUP_LDS_LAUNCH(X, P, D, C, B, F)                                                                      \
+  do {                                                                                                          \
+    PSOUP_DEDISP_TRACE((lds_tag<X, P, D, C, B>()));                                                             \
+    dedisperse_lds_kernel<X, P, D, C, B><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive, d_offT, \
+                                                              ldo, d_base, d_skip, ndm + d_skip, d_wmin,         \
+                                                              out_nsamps, out, out_stride, scale, F);            \
+  } while (0)
   if (bytes) {
     if (dpt == 4)
-      dedisperse_lds_kernel<false, 1, 4, 1, true><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive,
-                                                                       d_offT, ldo, d_base, d_skip, ndm + d_skip,
-                                                                       d_wmin, out_nsamps, out, out_stride, scale,
-                                                                       flush);
+      PSOUP_LDS_LAUNCH(false, 1, 4, 1, true, flush);
     else
-      dedisperse_lds_kernel<false, 1, 2, 1, true><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive,
-                                                                       d_offT, ldo, d_base, d_skip, ndm + d_skip,
-                                                                       d_wmin, out_nsamps, out, out_stride, scale,
-                                                                       flush);
+      PSOUP_LDS_LAUNCH(false, 1, 2, 1, true, flush);
     post_launch_check("dedisperse_lds_kernel", s);
     return;
   }
-#define PSOUP_LDS_LAUNCH(X, P, D, C)                                                                           \
-  dedisperse_lds_kernel<X, P, D, C><<<grid, 256, 0, s>>>(chan_major, chan_stride, d_active, nactive, d_offT, ldo, \
-                                                         d_base, d_skip, ndm + d_skip, d_wmin, out_nsamps, out,      \
-                                                         out_stride, scale, 255)
-#define PSOUP_LDS_ONE(X)          \
-  if (two)                         \
-    PSOUP_LDS_LAUNCH(X, 2, 4, 1);  \
-  else if (dpt == 2)               \
-    PSOUP_LDS_LAUNCH(X, 1, 2, 1);  \
-  else                             \
-    PSOUP_LDS_LAUNCH(X, 1, 4, 1);
+#define PSOUP_LDS_ONE(X)                      \
+  if (two)                                     \
+    PSOUP_LDS_LAUNCH(X, 2, 4, 1, false, 255);  \
+  else if (dpt == 2)                           \
+    PSOUP_LDS_LAUNCH(X, 1, 2, 1, false, 255);  \
+  else                                         \
+    PSOUP_LDS_LAUNCH(X, 1, 4, 1, false, 255);
   if (xr) {
     PSOUP_LDS_ONE(true)
   } else {
@@ -1152,6 +1200,7 @@ void pack2_rows(const int8_t* chan_major, uint64_t chan_stride, int nrows, uint3
   PSOUP_CHECK(16 * (dw0 + ndw) <= chan_stride && dw0 + ndw <= stride2, "pack2_rows: past the rows");
   PSOUP_CHECK(nrows <= 65535, "pack2_rows: too many rows");
   dim3 grid(static_cast<unsigned>(std::min<uint64_t>((ndw + 255) / 256, 1024)), static_cast<unsigned>(nrows));
+  PSOUP_DEDISP_TRACE("pack2");
   pack2_kernel<<<grid, 256, 0, s>>>(chan_major, chan_stride, out, stride2, dw0, ndw);
   post_launch_check("pack2_kernel", s);
 }
@@ -1190,14 +1239,18 @@ void dedisperse_2bit(const uint32_t* x2, uint64_t stride2, const int32_t* d_acti
   const int d_base = d0 / (4 * dpw) * (4 * dpw), d_skip = d0 - d_base;
   dim3 grid(static_cast<unsigned>((ndm + d_skip + 4 * dpw - 1) / (4 * dpw)), static_cast<unsigned>(ty));
   PSOUP_CHECK(d_base + static_cast<int>(grid.x) * 4 * dpw <= ldo, "dedisperse_2bit: offset table too narrow");
+#define PSOUP_2BIT_LAUNCH(W)                                                                                    \
+  do {                                                                                                          \
+    PSOUP_DEDISP_TRACE((twobit_tag<W>()));                                                                      \
+    dedisperse_2bit_kernel<W><<<grid, 256, 0, s>>>(x2, stride2, d_active, nactive, d_offT, ldo, d_base, d_skip,  \
+                                                   ndm + d_skip, d_wmin, dedisperse_2bit_window(max_spread) / 4, \
+                                                   out_nsamps, out, out_stride, scale);                          \
+  } while (0)
   if (dpw == 2)
-    dedisperse_2bit_kernel<2><<<grid, 256, 0, s>>>(x2, stride2, d_active, nactive, d_offT, ldo, d_base, d_skip,
-                                                   ndm + d_skip, d_wmin, dedisperse_2bit_window(max_spread) / 4,
-                                                   out_nsamps, out, out_stride, scale);
+    PSOUP_2BIT_LAUNCH(2);
   else
-    dedisperse_2bit_kernel<4><<<grid, 256, 0, s>>>(x2, stride2, d_active, nactive, d_offT, ldo, d_base, d_skip,
-                                                   ndm + d_skip, d_wmin, dedisperse_2bit_window(max_spread) / 4,
-                                                   out_nsamps, out, out_stride, scale);
+    PSOUP_2BIT_LAUNCH(4);
+#undef PSOUP_2BIT_LAUNCH
   post_launch_check("dedisperse_2bit_kernel", s);
 }
 

@@ -715,6 +715,8 @@ PYBIND11_MODULE(_C, m) {
     kern::dedisperse_direct(P<const int8_t>(x), stride, nchans, P<const int32_t>(offsets), P<const int32_t>(kill), ndm,
                             out_nsamps, P<uint8_t>(out), out_stride, scale, bias, nactive, S(s));
   });
+  k.def("dedisp_trace", &kern::dedisp_trace, py::arg("on"));
+  k.def("dedisp_trace_take", &kern::dedisp_trace_take);
   k.def("u8_to_f32_pad", [](uintptr_t in, uint64_t nvalid, uintptr_t out, uint64_t n, uintptr_t sum, uintptr_t s) {
     kern::u8_sum(P<const uint8_t>(in), nvalid, P<unsigned long long>(sum), S(s));
     kern::u8_to_f32_pad(P<const uint8_t>(in), nvalid, P<float>(out), n, P<const unsigned long long>(sum), S(s));
