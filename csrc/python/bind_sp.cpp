@@ -166,4 +166,32 @@ void bind_sp(py::module_& m) {
         return py::make_tuple(ev, eng.reruns(), o_snr, o_arg);
       },
       py::arg("rows"), py::arg("nsamps"), py::arg("params"), py::arg("dense") = true, py::arg("dm_idx0") = 0);
+
+  // Trend and sigma driver for tests: the two launches that precede the
+  // search, on host rows [ndm, stride].  Returns (means float32 [ndm, nblk],
+  // partials float64 [ndm, kSpSigmaParts]): the trend block means and the
+  // partial sums of (u - trend)^2, neither of which leaves the engine.
+  m.def(
+      "sp_trend_sigma_rows",
+      [](py::array_t<uint8_t, py::array::c_style> rows, uint64_t nsamps, uint64_t baseline_samples) -> py::tuple {
+        PSOUP_CHECK(rows.ndim() == 2, "sp_trend_sigma_rows: rows must be [ndm, stride]");
+        const int ndm = static_cast<int>(rows.shape(0));
+        const uint64_t stride = static_cast<uint64_t>(rows.shape(1));
+        PSOUP_CHECK(ndm > 0 && stride >= nsamps, "sp_trend_sigma_rows: stride shorter than nsamps");
+        PSOUP_CHECK(baseline_samples > 0 && baseline_samples <= nsamps, "sp_trend_sigma_rows: trend block length");
+        const size_t nblk = (nsamps + baseline_samples - 1) / baseline_samples;
+        DeviceBuffer<uint8_t> d_rows(static_cast<size_t>(ndm) * stride);
+        PSOUP_HIP_CHECK(hipMemcpy(d_rows.data(), rows.data(), d_rows.bytes(), hipMemcpyHostToDevice));
+        DeviceBuffer<float> d_means(static_cast<size_t>(ndm) * nblk);
+        DeviceBuffer<double> d_part(static_cast<size_t>(ndm) * kern::kSpSigmaParts);
+        kern::sp_block_means(d_rows.data(), stride, ndm, nsamps, baseline_samples, d_means.data(), nullptr);
+        kern::sp_sigma(d_rows.data(), stride, ndm, nsamps, baseline_samples, d_means.data(), d_part.data(), nullptr);
+        PSOUP_HIP_CHECK(hipStreamSynchronize(nullptr));
+        py::array_t<float> a_means({static_cast<size_t>(ndm), nblk});
+        py::array_t<double> a_part({static_cast<size_t>(ndm), static_cast<size_t>(kern::kSpSigmaParts)});
+        PSOUP_HIP_CHECK(hipMemcpy(a_means.mutable_data(), d_means.data(), d_means.bytes(), hipMemcpyDeviceToHost));
+        PSOUP_HIP_CHECK(hipMemcpy(a_part.mutable_data(), d_part.data(), d_part.bytes(), hipMemcpyDeviceToHost));
+        return py::make_tuple(a_means, a_part);
+      },
+      py::arg("rows"), py::arg("nsamps"), py::arg("baseline_samples"));
 }

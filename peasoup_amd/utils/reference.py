@@ -945,6 +945,240 @@ def sp_block_maxima(snr: Sequence[np.ndarray], block: int = 64):
     return out
 
 
+SP_EPS32 = 2.0 ** -23  # float32 machine epsilon: twice the unit roundoff of one rounded operation
+
+
+def sp_block_means(u8: np.ndarray, baseline: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(exact int64 sum, sample count) of every trend block."""
+    u = np.asarray(u8).astype(np.int64)
+    n = len(u)
+    nblk = (n + baseline - 1) // baseline
+    sums = np.array([u[b * baseline:(b + 1) * baseline].sum() for b in range(nblk)], dtype=np.int64)
+    counts = np.array([min(n, (b + 1) * baseline) - b * baseline for b in range(nblk)], dtype=np.int64)
+    return sums, counts
+
+
+def sp_sigma(u8: np.ndarray, baseline: int) -> float:
+    """sqrt(mean((u8 - trend)^2)) over all n samples, as in sp_boxcar_snr."""
+    x = np.asarray(u8, dtype=np.float64) - sp_trend(u8, baseline)
+    return math.sqrt(float(np.mean(x * x)))
+
+
+def _sp_trend_error(u8: np.ndarray, baseline: int) -> np.ndarray:
+    """Per sample: bound on |float32 kernel trend - sp_trend| (see sp_error_bound)."""
+    u = np.asarray(u8)
+    n = len(u)
+    sums, counts = sp_block_means(u, baseline)
+    M = sums / counts.astype(np.float64)
+    t = sp_trend(u, baseline)
+    nblk = len(M)
+    if nblk == 1:
+        return SP_EPS32 * np.abs(t)  # means[0] is returned as it is: one rounding
+    pos = (np.arange(n, dtype=np.float64) - 0.5 * baseline) / baseline
+    b = np.clip(np.floor(pos).astype(np.int64), 0, nblk - 2)
+    m_abs = np.maximum(np.abs(M[b]), np.abs(M[b + 1]))
+    d = np.abs(M[b + 1] - M[b])
+    # At an exact block centre the kernel's double pos may fall a rounding
+    # below the integer: it then interpolates in the block before, fr ~ 1.
+    dl = np.abs(np.diff(M))
+    dmax = np.maximum(np.concatenate([[0.0], dl]), np.concatenate([dl, [0.0]]))  # per centre: both neighbours
+    j = np.rint(pos)
+    centre = (np.abs(pos - j) < 1e-6) & (j >= 0) & (j <= nblk - 1)
+    jj = np.clip(j.astype(np.int64), 0, nblk - 1)
+    d = np.where(centre, dmax[jj], d)
+    m_abs = np.where(centre, np.maximum(m_abs, np.abs(M[np.clip(jj - 1, 0, nblk - 1)])), m_abs)
+    e = SP_EPS32 * (m_abs + 3.0 * d + np.abs(t))
+    flat = ((pos <= 0) | (pos >= nblk - 1)) & ~centre
+    return np.where(flat, SP_EPS32 * np.abs(t), e)
+
+
+def sp_sigma_rel_bound(u8: np.ndarray, baseline: int) -> float:
+    """Bound on |kernel sigma - oracle sigma| / sigma.  The kernel's sigma is
+    the root mean square (in double) of x^ = fl32(u - t^); with x^ = x + d,
+    |d_i| <= e_t[i] + eps32 |x_i| (trend error, one subtraction), the
+    triangle inequality on the 2-norm gives |sigma^ - sigma| <= rms(e_t) +
+    eps32 sigma.  The double accumulation, division and root add a few 2^-53
+    n, covered by 1e-12.  Zero for a constant row (both sigmas are 0)."""
+    sigma = sp_sigma(u8, baseline)
+    if sigma == 0:
+        return 0.0
+    e_t = _sp_trend_error(u8, baseline)
+    return math.sqrt(float(np.mean(e_t * e_t))) / sigma + SP_EPS32 + 1e-12
+
+
+def sp_error_bound(u8: np.ndarray, baseline: int, widths) -> List[np.ndarray]:
+    """Per width w = 2^k: float64 array over the starts 0..n - w, a worst-case
+    bound on |kernel S/N - sp_boxcar_snr|, from the kernel's arithmetic and
+    oracle quantities only.  Every rounded float32 operation is charged eps32 =
+    2^-23 (relative), twice its unit roundoff: the factor of two pays for all
+    second-order terms, for the double arithmetic of pos and for the contraction
+    of a multiply-add, which only removes a rounding.
+
+    Trend t^ = fl(m0 + fl(fr fl(m1 - m0))), M the exact means, d = |M1 - M0|:
+      means rounded to float32         max(|M0|, |M1|) eps32
+      fr = fl32(pos - b), |dfr| eps32  d eps32
+      the difference, the product      2 d eps32
+      the sum                          |t| eps32
+    so e_t = eps32 (max|M| + 3 d + |t|) <= 5 * 255 eps32; where the trend is
+    flat (before the first centre, past the last, one block) a mean is returned
+    as it is and e_t = eps32 |t|.
+    Staged y^ = fl(fl(u - t^) fl32(1 / sigma^)): the subtraction, the rounding
+    of 1 / sigma^ and the product cost 3 eps32 |y|, sigma^ itself r' |y| with
+    r' = r / (1 - r), r = sp_sigma_rel_bound:  e_y = e_t / sigma + (3 eps32 + r') |y|.
+    A dyadic sum of 2^k terms passes every term through k additions:
+    k eps32 sum|y^|; the scale (a float32 constant, one product) 2 eps32.  With
+    sum|y^| <= sum(|y| + e_y):
+
+      bound_w[i] = ((1 + (k + 2) eps32) sum e_y + (k + 2) eps32 sum|y|) / sqrt(w)
+                <= eps32 (c1 255 sqrt(w) / sigma + (k + c2) sum|y| / sqrt(w)),
+      c1 = 5 (1 + 15 eps32), c2 = 5 + r' / eps32,
+
+    the sums over the window [i, i + w).  All zeros for a constant row: the
+    kernel's means, residuals and sigma are then exactly 0 and so is its S/N."""
+    u = np.asarray(u8)
+    n = len(u)
+    x = u.astype(np.float64) - sp_trend(u, baseline)
+    sigma = math.sqrt(float(np.mean(x * x)))
+    if sigma == 0:
+        return [np.zeros(n + 1 - w) for w in widths]
+    r = sp_sigma_rel_bound(u, baseline)
+    r = r / (1.0 - r)
+    y = np.abs(x) / sigma
+    e_y = _sp_trend_error(u, baseline) / sigma + (3.0 * SP_EPS32 + r) * y
+    cy = np.concatenate([[0.0], np.cumsum(y)])
+    ce = np.concatenate([[0.0], np.cumsum(e_y)])
+    out = []
+    for w in widths:
+        k = int(w).bit_length() - 1
+        assert 1 << k == w
+        sy = cy[w:n + 1] - cy[:n + 1 - w]
+        se = ce[w:n + 1] - ce[:n + 1 - w]
+        out.append(((1.0 + (k + 2) * SP_EPS32) * se + (k + 2) * SP_EPS32 * sy) / math.sqrt(w))
+    return out
+
+
+def sp_scale32(k: int) -> np.float32:
+    """The search's float32 scale 2^(-k / 2) of level k: exact for even k, the
+    rounded 1 / sqrt(2) over a power of two for odd k."""
+    if k & 1:
+        return np.float32(np.float32(0.70710678118654752) / np.float32(1 << (k >> 1)))
+    return np.float32(1.0 / (1 << (k >> 1)))
+
+
+def sp_boxcar_snr_exact(u8: np.ndarray, widths) -> Dict:
+    """Integer-exact single-pulse S/N for a row whose trend is one block (the
+    baseline is the row) with an integer mean and whose sigma is a power of
+    two.  Then x = u - mean are integers, x / sigma and every window sum of
+    them are exact in float32 (|sum| sigma < 2^24) in any order, and the only
+    rounding is the product with the float32 scale of the level.  Returns
+    sums (int64 per width), sigma, snr (float64 sums / (sigma sqrt(w))) and
+    snr32: the float32 the search must return, fl32(sum / sigma * scale32(k)),
+    the product exact in float64."""
+    u = np.asarray(u8).astype(np.int64)
+    n = len(u)
+    tot = int(u.sum())
+    assert tot % n == 0, "sp_boxcar_snr_exact: the mean must be an integer"
+    x = u - tot // n
+    sumsq = int((x * x).sum())
+    sigma = math.sqrt(sumsq / n)
+    assert sigma > 0 and math.frexp(sigma)[0] == 0.5 and sigma * sigma * n == sumsq, \
+        "sp_boxcar_snr_exact: sigma must be a power of two"
+    c = np.concatenate([[0], np.cumsum(x)])
+    sums, snr, snr32 = [], [], []
+    for w in widths:
+        k = int(w).bit_length() - 1
+        s = c[w:n + 1] - c[:n + 1 - w]
+        assert np.abs(s).max() * max(sigma, 1.0) < 2 ** 24
+        sums.append(s)
+        snr.append(s / (sigma * math.sqrt(w)))
+        snr32.append(((s / sigma) * float(sp_scale32(k))).astype(np.float32))
+    return dict(sums=sums, sigma=sigma, snr=snr, snr32=snr32)
+
+
+def sp_search_f32(u8: np.ndarray, baseline: int, kmax: int, tile: int = 8192, halo_max: int = 4096,
+                  block: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+    """Float32 NumPy emulation of the search in its own order, per tile of
+    `tile` starts with a window of tile + 2^kmax samples: float32 means and
+    trend, sigma from float32 residuals summed in double, staging (samples past
+    n are zero), widths 1..8 from twelve staged samples per group of four,
+    then B_2w[i] = B_w[i] + B_w[i + w] with the window's guards (a group whose
+    partner lies past the window keeps its value, and its stale copy in the
+    window).  Unstaged window memory is NaN, so a result that depended on it
+    would show.  Returns (best float32, arg uint32) [kmax + 1, ceil(n / 64)]
+    as the search's dense outputs: the lowest index on a tie, 0 and 0xffffffff
+    where a block holds no valid start."""
+    f32 = np.float32
+    u = np.asarray(u8)
+    n = len(u)
+    sums, counts = sp_block_means(u, baseline)
+    means = (sums / counts.astype(np.float64)).astype(f32)
+    nblk = len(means)
+    if nblk == 1:
+        trend = np.full(n, means[0], dtype=f32)
+    else:
+        pos = (np.arange(n, dtype=np.float64) - 0.5 * baseline) * (1.0 / baseline)
+        b = np.clip(pos.astype(np.int64), 0, nblk - 2)
+        fr = (pos - b).astype(f32)
+        m0 = means[b]
+        trend = (m0 + (fr * (means[b + 1] - m0)).astype(f32)).astype(f32)
+        trend = np.where(pos <= 0.0, means[0], trend)
+        trend = np.where(pos >= nblk - 1, means[nblk - 1], trend).astype(f32)
+    x = (u.astype(f32) - trend).astype(f32)
+    sigma = math.sqrt(float((x.astype(np.float64) ** 2).sum()) / n)
+    inv_sigma = f32(1.0 / sigma) if sigma > 0 else f32(0)
+    y = (x * inv_sigma).astype(f32)
+
+    H = 1 << kmax
+    L = tile + H
+    ngroups = (tile + halo_max) // 4
+    own = tile // 4
+    gi = 4 * np.arange(ngroups)
+    four = np.arange(4)
+    nb64 = (n + block - 1) // block
+    best = np.zeros((kmax + 1, nb64), dtype=f32)
+    arg = np.full((kmax + 1, nb64), 0xFFFFFFFF, dtype=np.uint32)
+
+    def emit(k, t0, sums_own):
+        w = 1 << k
+        vals = (sums_own.reshape(-1) * sp_scale32(k)).astype(f32)  # starts t0 .. t0 + tile - 1
+        start = t0 + np.arange(tile)
+        valid = start + w <= n
+        masked = np.where(valid, vals, -np.inf).reshape(-1, block)
+        nanrow = (np.isnan(vals) & valid).reshape(-1, block).any(axis=1)
+        j = np.argmax(np.where(np.isnan(masked), -np.inf, masked), axis=1)  # first occurrence
+        for r in range(tile // block):
+            blk = t0 // block + r
+            if blk >= nb64 or not valid[r * block:(r + 1) * block].any():
+                continue
+            best[k, blk] = np.nan if nanrow[r] else masked[r, j[r]]
+            arg[k, blk] = t0 + r * block + j[r]
+
+    for t0 in range(0, n, tile):
+        lds = np.full(tile + halo_max + 8, np.nan, dtype=f32)
+        nst = (L + 8) // 4 * 4
+        lds[:nst] = 0
+        m = max(0, min(n - t0, nst))
+        lds[:m] = y[t0:t0 + m]
+        act = gi + 4 <= L
+        Y = np.where(act[:, None], lds[np.minimum(gi[:, None] + np.arange(12)[None, :], len(lds) - 1)], f32(0))
+        b2 = (Y[:, :10] + Y[:, 1:11]).astype(f32)
+        b4 = (b2[:, :8] + b2[:, 2:10]).astype(f32)
+        B = (b4[:, :4] + b4[:, 4:8]).astype(f32)
+        for k, lv in enumerate([Y[:, :4], b2[:, :4], b4[:, :4], B]):
+            if k <= kmax:
+                emit(k, t0, lv[:own])
+        lds[(gi[act][:, None] + four[None, :])] = B[act]
+        for k in range(4, kmax + 1):
+            w = 1 << (k - 1)
+            ok = gi + w + 4 <= L
+            B[ok] = (B[ok] + lds[(gi[ok] + w)[:, None] + four[None, :]]).astype(f32)
+            emit(k, t0, B[:own])
+            if k == kmax:
+                break
+            lds[(gi[ok][:, None] + four[None, :])] = B[ok]
+    return best, arg
+
+
 def sp_cluster_ref(events, dm_list, band_delay_per_dm: float, tsamp: float) -> List[Dict]:
     """Literal transcription of the clustering rule.  events: (sample,
     width_log2, snr, dm_idx) tuples.  Taken in descending S/N (ties: dm_idx,
