@@ -126,6 +126,7 @@ void bind_burst(py::module_& m); // bind_burst.cpp
 void bind_opt(py::module_& m);   // bind_opt.cpp
 void bind_scrunch(py::module_& m);  // bind_scrunch.cpp
 void bind_digi(py::module_& m);     // bind_digi.cpp
+void bind_fits(py::module_& m);     // bind_fits.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -703,6 +704,7 @@ PYBIND11_MODULE(_C, m) {
   bind_opt(m);
   bind_scrunch(m);
   bind_digi(m);
+  bind_fits(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

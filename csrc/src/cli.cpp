@@ -2,6 +2,7 @@
 #include "psoup/burstcube.hpp"
 #include "psoup/cubeopt.hpp"
 #include "psoup/digi.hpp"
+#include "psoup/psrfits.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
 #include "psoup/scrunch.hpp"
@@ -662,6 +663,63 @@ bool parse_digi_cmdline(DigiCmdLineOptions& a, const std::vector<std::string>& a
   }
   if (a.rescale_blocks < 0) {
     std::cerr << "Error: --rescale_blocks must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_fits_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_fits2fil.fil", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_fits_cmdline(FitsCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_fits_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (search-mode PSRFITS of 1, 2, 4, 8 or 16 bits)", a.infilename, true),
+      val_s("o", "outfilename", "The filterbank written (8 bits, descending frequency)", a.outfilename),
+      val_s("k", "killfile", "Channel mask file (input channel order)", a.killfilename),
+      val_s("", "kill_out", "Output killfile (output channel order): 0 = killed or dead", a.killoutfilename),
+      val_n("", "sigma_out", "Noise sigma of a channel in the 8-bit output", a.sigma_out),
+      val_s("", "scale", "channel: one gain per channel (flattens the bandpass); file: one gain for all", a.scale),
+      val_n("", "rescale_blocks", "Blocks of 4096 samples per rescaling interval (0 = one for the file)",
+            a.rescale_blocks),
+      val_s("", "pol", "auto (AABB: sum of 0 and 1; IQUV: 0) or the index of the one polarisation to take", a.pol),
+      sw("", "no_scales", "Take DAT_SCL as 1", a.no_scales),
+      sw("", "no_offsets", "Take DAT_OFFS as 0", a.no_offsets),
+      sw("", "no_weights", "Take DAT_WTS as 1", a.no_weights),
+      val_n("", "telescope_id", "telescope_id written (default: from TELESCOP)", a.telescope_id),
+      val_n("", "machine_id", "machine_id written", a.machine_id),
+      sw("v", "verbose", "verbose mode: print rows, dropped slots, polarisations, z, nbad, nclip, live count, gains",
+         a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup fits2fil extension - search-mode PSRFITS to an 8-bit filterbank", nullptr,
+                  exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (!(a.sigma_out > 0) || !(a.sigma_out < 1e9)) {
+    std::cerr << "Error: --sigma_out must be positive" << std::endl;
+    return false;
+  }
+  if (a.scale != "channel" && a.scale != "file") {
+    std::cerr << "Error: --scale must be channel or file" << std::endl;
+    return false;
+  }
+  if (a.rescale_blocks < 0) {
+    std::cerr << "Error: --rescale_blocks must be non-negative" << std::endl;
+    return false;
+  }
+  bool pol_ok = a.pol == "auto" || (!a.pol.empty() && a.pol.size() <= 2);
+  if (a.pol != "auto")
+    for (char c : a.pol) pol_ok = pol_ok && std::isdigit(static_cast<unsigned char>(c));
+  if (!pol_ok) {
+    std::cerr << "Error: --pol must be auto or a polarisation index" << std::endl;
+    return false;
+  }
+  if (a.telescope_id < -1 || a.machine_id < 0) {
+    std::cerr << "Error: --telescope_id and --machine_id must be non-negative" << std::endl;
     return false;
   }
   return true;

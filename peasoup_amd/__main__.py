@@ -6,7 +6,8 @@ burst [burstcube flags]`` for the cutouts of single-pulse candidates, ``python
 -m peasoup_amd opt [cubeopt flags]`` for the DM / period / acceleration search
 on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
 scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``python -m peasoup_amd digi
-[fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank) -- the peasoup CLI as a
+[fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank, ``python -m peasoup_amd
+fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -84,6 +85,8 @@ def main(argv=None) -> int:
         return _main_scrunch(["filscrunch"] + argv[2:])
     if len(argv) > 1 and argv[1] == "digi":
         return _main_digi(["fildigi"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "fits":
+        return _main_fits(["fits2fil"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -264,6 +267,29 @@ def _main_digi(argv) -> int:
         _fail_hard("digi", e)
     if res is not None and args.verbose:
         print(f"fildigi: {res['nsamps']} samples x {res['nchans']} channels, nbad {int(res['nbad'].sum())}, nclip "
+              f"{res['nclip']}, {res['nlive']} of {res['nchans']} channels live, gains {res['gain_min']:g} to "
+              f"{res['gain_max']:g}")
+    return 0
+
+
+def _main_fits(argv) -> int:
+    from . import _C
+    from .models.psrfits import convert_psrfits
+
+    ok, exit_now, args = _C.parse_fits_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = convert_psrfits(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("fits", e)
+    if res is not None and args.verbose:
+        pols = "+".join(str(p) for p in res["pols"] if p >= 0)
+        print(f"fits2fil: {res['rows']} rows, {res['ndropped']} dropped slots, polarisations {pols}, z {res['z']:g}, "
+              f"{res['nsamps']} samples x {res['nchans']} channels, nbad {int(res['nbad'].sum())}, nclip "
               f"{res['nclip']}, {res['nlive']} of {res['nchans']} channels live, gains {res['gain_min']:g} to "
               f"{res['gain_max']:g}")
     return 0

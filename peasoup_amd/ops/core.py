@@ -915,3 +915,66 @@ def digitise(data: np.ndarray, foff: float, sigma_out: float = 16.0, scale: str 
     res["launches"] = int(dig.launches)
     res["chunk_samples"] = int(dig.chunk_samples)
     return y, res
+
+
+# ---------------------------------------------------------------- fits2fil --
+def fits_decode(data: torch.Tensor, scl: torch.Tensor, offs: torch.Tensor, wts: torch.Tensor, slot_row, nsblk: int,
+                nbits: int, signed: bool = False, pols: Tuple[int, int] = (0, -1), z: float = 0.0, t0: int = 0,
+                count: Optional[int] = None) -> torch.Tensor:
+    """Decodes PSRFITS rows on the device (csrc/kernels/psrfits.hip).  data:
+    uint8 [nrows, nsblk * npol * nchan * nbits / 8], the DATA fields as in the
+    file; scl, offs float32 [nrows, npol, nchan]; wts float32 [nrows, nchan];
+    slot_row: the file row of every output slot of nsblk samples, -1 for a
+    dropped one.  Returns x float32 [count, nchan], samples [t0, t0 + count):
+    bit for bit ``utils.reference.fits_decode``."""
+    _check(data, torch.uint8, "data")
+    for t, name in ((scl, "scl"), (offs, "offs"), (wts, "wts")):
+        _check(t, torch.float32, name)
+    if scl.dim() != 3 or offs.shape != scl.shape or wts.dim() != 2 or data.dim() != 2:
+        raise ValueError("scl and offs must be [nrows, npol, nchan], wts [nrows, nchan], data [nrows, bytes]")
+    nrows, npol, nchan = (int(v) for v in scl.shape)
+    if tuple(wts.shape) != (nrows, nchan) or data.shape[0] != nrows:
+        raise ValueError("data, scl, offs and wts must hold the same rows and channels")
+    if nbits not in (1, 2, 4, 8, 16) or (nchan * nbits) % 8 or nsblk < 1:
+        raise ValueError("nbits must be 1, 2, 4, 8 or 16 with nchan * nbits a multiple of 8")
+    if data.shape[1] != nsblk * npol * nchan * nbits // 8:
+        raise ValueError("data must hold nsblk * npol * nchan * nbits / 8 bytes per row")
+    slot_row = [int(r) for r in slot_row]
+    nsamps = len(slot_row) * nsblk
+    count = nsamps - t0 if count is None else int(count)
+    if t0 < 0 or count < 1 or t0 + count > nsamps:
+        raise ValueError("[t0, t0 + count) must lie within the slots")
+    a, b = int(pols[0]), int(pols[1])
+    if not 0 <= a < npol or not -1 <= b < npol:
+        raise ValueError("polarisation out of range")
+    k0, k1 = t0 // nsblk, (t0 + count - 1) // nsblk
+    out = torch.empty((count, nchan), dtype=torch.float32, device=data.device)
+    _C.fits_decode_raw(data.data_ptr(), scl.data_ptr(), offs.data_ptr(), wts.data_ptr(), nrows, slot_row[k0:k1 + 1],
+                       int(nsblk), npol, nchan, int(nbits), bool(signed), a, b, float(np.float32(z)), int(t0), count,
+                       out.data_ptr(), _s())
+    return out
+
+
+def fits_digitise(file_bytes, sigma_out: float = 16.0, scale: str = "channel", rescale_blocks: int = 0, killmask=None,
+                  pol: int = -1, no_scales: bool = False, no_offsets: bool = False, no_weights: bool = False,
+                  telescope_id: int = -1, machine_id: int = 0, rawdatafile: str = "",
+                  budget_bytes: Optional[int] = None):
+    """fits2fil on a search-mode PSRFITS file held in host memory (bytes or a
+    uint8 NumPy array): decode, block sums, host scale, requantise
+    (``_C.FitsDigitiser``), in time chunks of whole blocks.  Returns (y uint8
+    NumPy [nsamps, nchan] in output channel order, the result dict: header,
+    rows, ndropped, pols, z, N, S1, S2, E, nbad, mean, gain, live, killmask,
+    nclip, chunks, launches, ...).  Equals ``utils.reference.fits_filterbank``.
+    Everything is validated before anything is launched (``NativeError``)."""
+    buf = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(file_bytes, dtype=np.uint8).reshape(-1)
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    kw = {} if budget_bytes is None else {"budget_bytes": int(budget_bytes)}
+    opt = _C.FitsOptions(int(pol), bool(no_scales), bool(no_offsets), bool(no_weights), int(telescope_id),
+                         int(machine_id))
+    dig = _C.FitsDigitiser(buf, opt, kill, _C.DigiParams(float(sigma_out), str(scale), int(rescale_blocks)),
+                           str(rawdatafile), _s(), **kw)
+    y, res = dig.run()
+    res["launches"] = int(dig.launches)
+    res["chunk_samples"] = int(dig.chunk_samples)
+    return y, res

@@ -1935,3 +1935,201 @@ def digi_filterbank(infile: str, outfile: str, sigma_out: float = 16.0, scale: s
         with open(kill_out, "w") as fo:
             fo.write("".join("1\n" if v else "0\n" for v in kill))
     return dict(sums, **sc, y=y, nclip=nclip, flip=flip, killmask=[int(v) for v in kill])
+
+
+# ---------------------------------------------------------------- fits2fil --
+# The oracle of csrc/include/psoup/psrfits.hpp, written from its definition.
+FITS_NAN = np.uint32(0x7FC00000)
+FITS_TELESCOPES = {"ARECIBO": 1, "OOTY": 2, "NANCAY": 3, "PARKES": 4, "JODRELL": 5, "GBT": 6, "GMRT": 7,
+                   "EFFELSBERG": 8, "LOFAR": 11, "VLA": 12, "MEERKAT": 64}
+
+
+def fits_pols(npol: int, pol_type: str, pol: int = -1) -> Tuple[int, int]:
+    """(a, b) with b = -1 when one polarisation is taken; ``pol`` -1 = auto."""
+    if pol >= 0:
+        if pol >= npol:
+            raise ValueError(f"fits: --pol {pol} is not below NPOL = {npol}")
+        return pol, -1
+    if npol == 1:
+        return 0, -1
+    t = pol_type.strip().upper()
+    if t.startswith("AABB"):
+        return 0, 1
+    if t == "IQUV":
+        return 0, -1
+    raise ValueError(f"fits: POL_TYPE '{pol_type}' with NPOL = {npol} needs --pol P")
+
+
+def fits_row_slots(offs_sub, nrows: int, nsblk: int, tbin: float) -> Dict:
+    """Rows and time: slot [nrows], slot_row [nslots] (-1 = dropped), nslots,
+    nsamps, ndropped, offs_sub0 (as tstart takes it)."""
+    half = (0.5 * nsblk) * tbin
+    if offs_sub is None or not np.any(np.asarray(offs_sub) != 0):
+        slot = np.arange(nrows, dtype=np.int64)
+        o0 = half
+    else:
+        o = np.asarray(offs_sub, np.float64)
+        if not np.isfinite(o).all():
+            raise ValueError("fits: OFFS_SUB is not finite")
+        q = (o - o[0]) / (float(nsblk) * tbin)
+        k = np.rint(q)
+        if (np.abs(q - k) > 1e-3).any():
+            raise ValueError("fits: a row does not start on a whole row")
+        slot = k.astype(np.int64)
+        if slot[0] != 0 or (np.diff(slot) <= 0).any():
+            raise ValueError("fits: the row slots do not increase strictly")
+        o0 = float(o[0]) if o[0] != 0 else half
+    nslots = int(slot[-1]) + 1
+    if nslots > 2 * nrows:
+        raise ValueError("fits: more than half the rows are dropped")
+    if nslots * nsblk >= 1 << 31:
+        raise ValueError("fits: too many samples for a SIGPROC header")
+    slot_row = np.full(nslots, -1, np.int32)
+    slot_row[slot] = np.arange(nrows, dtype=np.int32)
+    return {"slot": slot, "slot_row": slot_row, "nslots": nslots, "nsamps": nslots * nsblk,
+            "ndropped": nslots - nrows, "offs_sub0": o0}
+
+
+def fits_band(freq, chan_bw: float = 0.0) -> Tuple[float, float]:
+    """(fch1, foff) of the first row's DAT_FREQ (float64 [nchan])."""
+    f = np.asarray(freq, np.float64)
+    n = len(f)
+    fch1 = float(f[0])
+    foff = float(chan_bw) if n == 1 else float((f[n - 1] - f[0]) / float(n - 1))
+    if not (math.isfinite(fch1) and math.isfinite(foff)) or foff == 0:
+        raise ValueError("fits: foff must not be zero")
+    if (np.abs(f - (fch1 + np.arange(n, dtype=np.float64) * foff)) > 0.01 * abs(foff)).any():
+        raise ValueError("fits: DAT_FREQ is not evenly spaced")
+    return fch1, foff
+
+
+def fits_sexagesimal(text: str) -> float:
+    s = text.strip()
+    neg = s.startswith("-")
+    if s[:1] in ("+", "-"):
+        s = s[1:]
+    parts = s.split(":", 2)
+    if len(parts) != 3:
+        return 0.0
+    try:
+        h, m, sec = int(parts[0]), int(parts[1]), float(parts[2].strip().replace("D", "E").replace("d", "E"))
+    except ValueError:
+        return 0.0
+    if h < 0 or m < 0 or not sec >= 0 or not math.isfinite(sec):
+        return 0.0
+    v = (float(h) * 10000.0 + float(m) * 100.0) + sec
+    return -v if neg else v
+
+
+def fits_decode(raw: np.ndarray, scl, offs, wts, slot_row, pols, z: float = 0.0, t0: int = 0,
+                count: Optional[int] = None) -> np.ndarray:
+    """The decode of the definition.  raw: integer samples [nrows, nsblk, npol,
+    nchan]; scl, offs float32 [nrows, npol, nchan]; wts float32 [nrows, nchan];
+    slot_row [nslots] (file row or -1).  Float64 steps as defined and one
+    rounding to float32; returns x float32 [count, nchan] of samples [t0, t0 +
+    count) with the quiet NaN 0x7fc00000 for a dropped slot, a zero weight and
+    a NaN result."""
+    raw = np.asarray(raw)
+    nrows, nsblk, npol, nchan = raw.shape
+    slot_row = np.asarray(slot_row)
+    nsamps = len(slot_row) * nsblk
+    count = nsamps - t0 if count is None else count
+    scl = np.asarray(scl, np.float32).astype(np.float64)
+    offs = np.asarray(offs, np.float32).astype(np.float64)
+    wts32 = np.asarray(wts, np.float32)
+    zd = float(np.float32(z))
+    out = np.full((nsamps, nchan), FITS_NAN, np.uint32)
+    a, b = pols
+    with np.errstate(all="ignore"):
+        for k, r in enumerate(slot_row):
+            if r < 0:
+                continue
+            u = (raw[r, :, a, :].astype(np.float64) - zd) * scl[r, a][None, :] + offs[r, a][None, :]
+            if b >= 0:
+                ub = (raw[r, :, b, :].astype(np.float64) - zd) * scl[r, b][None, :] + offs[r, b][None, :]
+                u = u + ub
+            v = u * wts32[r].astype(np.float64)[None, :]
+            x = v.astype(np.float32).view(np.uint32)
+            x = np.where(np.isnan(v) | (wts32[r] == 0)[None, :], FITS_NAN, x)
+            out[k * nsblk:(k + 1) * nsblk] = x
+    return np.ascontiguousarray(out[t0:t0 + count]).view(np.float32)
+
+
+def fits_header(f: Dict, slots: Dict, band, telescope_id: int = -1, machine_id: int = 0, rawdatafile: str = "") -> Dict:
+    """The output's header dict from a ``read_psrfits`` dict."""
+    p = f["primary"]
+    fch1, foff = band
+    _, fch1, foff = digi_band(fch1, foff, f["nchan"])
+    half = (0.5 * f["nsblk"]) * f["tbin"]
+
+    def num(key):
+        return float(p[key].strip().replace("D", "E").replace("d", "E"))
+
+    secs = ((num("STT_SMJD") + num("STT_OFFS")) + slots["offs_sub0"]) - half
+    tel = telescope_id if telescope_id >= 0 else FITS_TELESCOPES.get(p.get("TELESCOP", "").strip().upper(), 0)
+    hdr = {"source_name": p.get("SRC_NAME", "").strip(), "rawdatafile": rawdatafile, "telescope_id": tel,
+           "machine_id": machine_id, "data_type": 1, "src_raj": fits_sexagesimal(p.get("RA", "")),
+           "src_dej": fits_sexagesimal(p.get("DEC", "")), "tstart": float(int(p["STT_IMJD"])) + secs / 86400.0,
+           "tsamp": f["tbin"], "fch1": fch1, "foff": foff, "nchans": f["nchan"], "nbits": 8, "nifs": 1,
+           "nsamples": slots["nsamps"], "barycentric": 0}
+    present = ["telescope_id", "machine_id", "barycentric", "src_raj", "src_dej", "tstart", "nsamples"]
+    try:
+        hdr["ibeam"] = int(p["BEAM_ID"].strip())
+        present.append("ibeam")
+    except (KeyError, ValueError):
+        pass
+    hdr["_present"] = present
+    return hdr
+
+
+def fits_filterbank(infile, outfile: Optional[str] = None, sigma_out: float = 16.0, scale: str = "channel", J: int = 0,
+                    killmask=None, kill_out: Optional[str] = None, pol: int = -1, no_scales: bool = False,
+                    no_offsets: bool = False, no_weights: bool = False, telescope_id: int = -1, machine_id: int = 0,
+                    rawdatafile: Optional[str] = None) -> Dict:
+    """The whole tool on the CPU: reads ``infile`` (a path or the file's
+    bytes), writes ``outfile`` (and the killfile ``kill_out`` in output channel
+    order) when given; returns x, the block tables, the scale dict, y, nclip,
+    flip, killmask, the header dict and its bytes."""
+    import os
+
+    from .psrfits import read_psrfits, unpack_samples
+    from .sigproc import header_bytes
+
+    f = read_psrfits(infile)
+    nrows, nsblk, npol, nchan = f["nrows"], f["nsblk"], f["npol"], f["nchan"]
+    slots = fits_row_slots(f["OFFS_SUB"], nrows, nsblk, f["tbin"])
+    band = fits_band(f["DAT_FREQ"][0], f["chan_bw"])
+    pols = fits_pols(npol, f["pol_type"], pol)
+    if not sigma_out > 0 or J < 0 or scale not in ("channel", "file"):
+        raise ValueError("bad digi parameters")
+    raw = unpack_samples(f["DATA"], f["nbits"], bool(f["signint"])).reshape(nrows, nsblk, npol, nchan)
+    scl = np.ones_like(f["DAT_SCL"]) if no_scales else f["DAT_SCL"]
+    offs = np.zeros_like(f["DAT_OFFS"]) if no_offsets else f["DAT_OFFS"]
+    wts = np.ones_like(f["DAT_WTS"]) if no_weights else f["DAT_WTS"]
+    kill = np.ones(nchan, np.int64) if killmask is None or len(killmask) == 0 else (np.asarray(killmask) != 0).astype(np.int64)
+    if len(kill) != nchan:
+        raise ValueError("fits: killmask size != NCHAN")
+    kill = kill * (wts != 0).any(axis=0)
+    if not kill.any():
+        raise ValueError("fits: no live channel")
+    if rawdatafile is None:
+        rawdatafile = os.path.basename(infile) if isinstance(infile, str) else ""
+    hdr = fits_header(f, slots, band, telescope_id, machine_id, rawdatafile)
+    x = fits_decode(raw, scl, offs, wts, slots["slot_row"], pols, f["z"])
+    sums = digi_block_sums(x)
+    sc = digi_scale(sums["N"], sums["S1"], sums["S2"], sums["E"], kill, sigma_out, scale, J)
+    flip = band[1] > 0
+    y, nclip = digi_quant(x, sc["mean"], sc["gain"], J, flip)
+    alive = sc["alive"][::-1] if flip else sc["alive"]
+    head = header_bytes(hdr, keep_present=True)
+    if outfile:
+        tmp = outfile + ".tmp"
+        with open(tmp, "wb") as fo:
+            fo.write(head)
+            fo.write(np.ascontiguousarray(y).tobytes())
+        os.replace(tmp, outfile)
+    if kill_out:
+        with open(kill_out, "w") as fo:
+            fo.write("".join("1\n" if v else "0\n" for v in alive))
+    return dict(sums, **sc, x=x, y=y, nclip=nclip, flip=flip, killmask=[int(v) for v in alive], header=hdr,
+                header_bytes=head, slots=slots, pols=pols, z=f["z"], rows=nrows)
