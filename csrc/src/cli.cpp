@@ -1,5 +1,6 @@
 #include "psoup/cli.hpp"
 #include "psoup/burstcube.hpp"
+#include "psoup/burstopt.hpp"
 #include "psoup/cubeopt.hpp"
 #include "psoup/digi.hpp"
 #include "psoup/psrfits.hpp"
@@ -546,6 +547,39 @@ bool parse_opt_cmdline(CubeOptCmdLineOptions& a, const std::vector<std::string>&
       !(a.pd_step < 1e6) || !(a.dm_half_range < 1e9f)) {
     std::cerr << "Error: --p_step, --pd_step, --dm_half_range and --limit must be finite and non-negative"
               << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_bopt_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_burstopt.bopt", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_bopt_cmdline(BurstOptCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_bopt_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "Burst cutouts to search (a burstcube output)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_n("", "nfine", "Fine DM rows around the candidate's DM (odd, 1..257)", a.nfine),
+      val_n("", "fine_half_range", "Fine DM rows span the candidate's DM -/+ this (0 = the spacing of two coarse rows)",
+            a.fine_half_range),
+      val_n("", "limit", "At most this many candidates from the top of the file", a.limit),
+      sw("v", "verbose", "verbose mode: one line per candidate", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup burst-optimiser extension - DM, width and time search on burst cutouts",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.nfine < 1 || a.nfine > 257 || a.nfine % 2 == 0) {
+    std::cerr << "Error: --nfine must be odd and in 1..257" << std::endl;
+    return false;
+  }
+  if (!(a.fine_half_range >= 0) || !(a.fine_half_range < 1e9) || a.limit < 0) {
+    std::cerr << "Error: --fine_half_range and --limit must be finite and non-negative" << std::endl;
     return false;
   }
   return true;

@@ -4,7 +4,8 @@ flags]`` for the single-pulse search, ``python -m peasoup_amd cube [foldcube
 flags]`` for the filterbank fold cubes of candidates, ``python -m peasoup_amd
 burst [burstcube flags]`` for the cutouts of single-pulse candidates, ``python
 -m peasoup_amd opt [cubeopt flags]`` for the DM / period / acceleration search
-on fold cubes, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
+on fold cubes, ``python -m peasoup_amd bopt [burstopt flags]`` for the DM / width / time search on burst
+cutouts, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
 scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``python -m peasoup_amd digi
 [fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank, ``python -m peasoup_amd
 fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file) -- the peasoup CLI as a
@@ -79,6 +80,8 @@ def main(argv=None) -> int:
         return _main_burst(["burstcube"] + argv[2:])
     if len(argv) > 1 and argv[1] == "opt":
         return _main_opt(["cubeopt"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "bopt":
+        return _main_bopt(["burstopt"] + argv[2:])
     if len(argv) > 1 and argv[1] == "clean":
         return _main_clean(["rficlean"] + argv[2:])
     if len(argv) > 1 and argv[1] == "scrunch":
@@ -204,6 +207,26 @@ def _main_opt(argv) -> int:
     if run is not None and args.verbose:
         print_records(run)
         print(f"Wrote {run.ncand} cubeopt records to {args.outfilename}")
+    return 0
+
+
+def _main_bopt(argv) -> int:
+    from . import _C
+    from .models.burstopt import print_records, run_burst_opt
+
+    ok, exit_now, args = _C.parse_bopt_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        run = run_burst_opt(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("bopt", e)
+    if run is not None and args.verbose:
+        print_records(run)
+        print(f"Wrote {run.ncand} burstopt records to {args.outfilename}")
     return 0
 
 

@@ -649,6 +649,71 @@ def cube_optimise(candidates, header: Dict, ndm: int = 64, np_: int = 65, npd: i
     return recs
 
 
+# --------------------------------------------------------------- burstopt --
+def burst_search(d_ds: torch.Tensor, d_dmt: torch.Tensor, sf: torch.Tensor, out=None):
+    """The search of burstopt alone (csrc/include/psoup/burstopt.hpp, step 3),
+    with explicit shifts and a leading candidate axis: ``d_ds`` int32 [ncand,
+    nsub, ntime], ``d_dmt`` int32 [ncand, ndm, ntime], ``sf`` int32 [ncand,
+    nfine, nsub], every shift in [-ntime, ntime].  Returns (best_val [ncand, 2,
+    nw], best_idx [ncand, 2, nw], curve [ncand, nw, ndm + nfine], curve_bin
+    [ncand, nw, ndm + nfine]), int32 tensors on the current device; exactly the
+    NumPy oracle's (utils.reference.burst_opt_search).  Tensors given on the
+    host are uploaded; the kernels read and write device memory through raw
+    addresses and the results stay on the device (in ``out``, four such
+    tensors, where given).  The shifts are checked before anything is launched
+    or written: ``ValueError`` naming the candidate."""
+    for t, name in ((d_ds, "d_ds"), (d_dmt, "d_dmt"), (sf, "sf")):
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name} must be int32")
+    if d_ds.dim() != 3 or d_dmt.dim() != 3 or sf.dim() != 3:
+        raise ValueError("d_ds [ncand, nsub, ntime], d_dmt [ncand, ndm, ntime], sf [ncand, nfine, nsub]")
+    ncand, nsub, ntime = (int(x) for x in d_ds.shape)
+    ndm, nfine = int(d_dmt.shape[1]), int(sf.shape[1])
+    if tuple(d_dmt.shape) != (ncand, ndm, ntime) or tuple(sf.shape) != (ncand, nfine, nsub):
+        raise ValueError("d_dmt must be [ncand, ndm, ntime] and sf [ncand, nfine, nsub] for d_ds's ncand, nsub and ntime")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d_ds, d_dmt, sf = (t.detach().to(dev).contiguous() for t in (d_ds, d_dmt, sf))
+    bad = ((sf < -ntime) | (sf > ntime)).reshape(ncand, -1).any(dim=1)
+    if bool(bad.any()):
+        raise ValueError(f"burst search: candidate {int(torch.nonzero(bad)[0])} has a shift outside [-ntime, ntime]")
+    opt = _C.BurstOptimiser(_C.BurstOptGeom(ntime, nsub, ndm), _C.BurstOptGrid(nfine, 0.0), _s())
+    nw = opt.nwidths
+    shapes = [(ncand,) + shape for shape in ((2, nw), (2, nw), (nw, ndm + nfine), (nw, ndm + nfine))]
+    if out is None:
+        out = [torch.empty(shape, dtype=torch.int32, device=dev) for shape in shapes]
+    else:
+        out = list(out)
+        if len(out) != 4 or any(t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != s or not t.is_contiguous()
+                                for t, s in zip(out, shapes)):
+            raise ValueError("out must be four contiguous int32 device tensors: best_val, best_idx [ncand, 2, nw], "
+                             "curve, curve_bin [ncand, nw, ndm + nfine]")
+    if ncand:
+        opt.search_device(d_ds.data_ptr(), d_dmt.data_ptr(), sf.data_ptr(), ncand, *(t.data_ptr() for t in out))
+    return tuple(out)
+
+
+def burst_optimise(candidates, header: Dict, nfine: int = 65, fine_half_range: float = 0.0, delays=None,
+                   batch_bytes: int = None) -> List[Dict]:
+    """burstopt on cutout dicts (``BurstCubeFile.candidate``'s keys) of a
+    burst-cutout file with ``header`` (nchans, tsamp, fch1, foff): one record
+    per candidate, exactly utils.reference.burst_optimise's.  ``delays``: the
+    float32 delay table (default: the header's).  Every candidate is validated
+    before anything is launched (``NativeError`` naming the candidate)."""
+    cands = list(candidates)
+    if not cands:
+        return []
+    nsub, ntime = (int(x) for x in np.asarray(cands[0]["ds_sums"]).shape)
+    ndm = int(np.asarray(cands[0]["dmt_sums"]).shape[0])
+    geom = _C.BurstOptGeom(ntime, nsub, ndm, int(header["nchans"]), float(header["tsamp"]), float(header["fch1"]),
+                           float(header["foff"]))
+    grid = _C.BurstOptGrid(int(nfine), float(fine_half_range))
+    if delays is None:
+        delays = _C.generate_delay_table(geom.nchans, geom.tsamp, geom.fch1, geom.foff)
+    kw = {} if batch_bytes is None else {"batch_bytes": int(batch_bytes)}
+    opt = _C.BurstOptimiser(geom, grid, _s(), **kw)
+    return opt.optimise([dict(c) for c in cands], [float(x) for x in delays])
+
+
 # ----------------------------------------------------------- burst cutouts --
 def burst_cube(chan_major: torch.Tensor, ds_offsets: torch.Tensor, dmt_offsets: torch.Tensor, samples, tscrunch,
                ntime: int = 256, nsub: int = 256, bias: int = 0, killmask=None, nsamps: int = None,

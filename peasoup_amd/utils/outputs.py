@@ -423,6 +423,89 @@ def burst_mean(sums, hits) -> np.ndarray:
     return out
 
 
+# ---------------------------------------------------------------- burstopt --
+BOPT_MAGIC = b"PSBOPT01"
+_BOPT_HEADER = struct.Struct("<8s8IQ4d")  # magic, ncand ntime nsub ndm nchans nbits nfine nw, nsamps, 4 doubles
+_BOPT_CAND = struct.Struct("<QIIqff7dqff8I")  # the input's six | 7 doubles | opt_sample | opt_dm coarse_dm | 8 u32
+BOPT_HEADER_FIELDS = ("ncand", "ntime", "nsub", "ndm", "nchans", "nbits", "nfine", "nw", "nsamps", "tsamp", "fch1",
+                      "foff", "fine_half_range")
+_BOPT_SCALARS = ("sample", "width", "tscrunch", "t0", "dm", "cand_snr", "snr", "snr_coarse", "snr_in", "snr_dm0",
+                 "frac_pos", "v", "mbar_ds", "opt_sample", "opt_dm", "coarse_dm", "opt_width", "opt_kf", "opt_bin",
+                 "coarse_row", "coarse_width", "coarse_bin", "flags")
+_BOPT_FLOATS = frozenset(("dm", "cand_snr", "snr", "snr_coarse", "snr_in", "snr_dm0", "frac_pos", "v", "mbar_ds",
+                          "opt_dm", "coarse_dm"))
+
+
+def _bopt_arrays(h: Dict):
+    nw, ndm, nf, ns, nt = (int(h[k]) for k in ("nw", "ndm", "nfine", "nsub", "ntime"))
+    return (("dms", "<f4", (ndm,)), ("dmf", "<f4", (nf,)), ("mbar_dmt", "<f8", (ndm,)), ("best_val", "<i4", (2, nw)),
+            ("best_idx", "<i4", (2, nw)), ("curve", "<i4", (nw, ndm + nf)), ("curve_bin", "<i4", (nw, ndm + nf)),
+            ("band", "<i4", (ns,)), ("profile", "<i4", (nt,)))
+
+
+def write_bopt_file(path: str, header: Dict, records: List[Dict]) -> None:
+    """Writes a burstopt result file byte for byte as the native
+    ``write_bopt_file`` (csrc/src/burstopt.cpp): little-endian ``PSBOPT01``,
+    uint32 ncand ntime nsub ndm nchans nbits nfine nw, uint64 nsamps, double
+    tsamp fch1 foff fine_half_range (80 bytes); per candidate uint64 sample,
+    uint32 width, uint32 tscrunch, int64 t0, float dm, float cand_snr (the
+    input's S/N), double snr snr_coarse snr_in snr_dm0 frac_pos v mbar_ds,
+    int64 opt_sample, float opt_dm coarse_dm, uint32 opt_width opt_kf opt_bin
+    coarse_row coarse_width coarse_bin flags and a zero (136 bytes), then float
+    dms[ndm], float dmf[nfine], double mbar_dmt[ndm], int32 best_val[2][nw],
+    best_idx[2][nw], curve[nw][ndm + nfine], curve_bin[nw][ndm + nfine],
+    band[nsub], profile[ntime].  ``header`` needs every field but ncand.
+    Written to a temporary file, then renamed."""
+    import os
+
+    h = dict(header, ncand=len(records))
+    blob = [_BOPT_HEADER.pack(BOPT_MAGIC, *(int(h[k]) for k in BOPT_HEADER_FIELDS[:9]),
+                              *(float(h[k]) for k in BOPT_HEADER_FIELDS[9:]))]
+    for i, r in enumerate(records):
+        blob.append(_BOPT_CAND.pack(*((float if k in _BOPT_FLOATS else int)(r[k]) for k in _BOPT_SCALARS), 0))
+        for name, dt, shape in _bopt_arrays(h):
+            a = np.ascontiguousarray(r[name], dtype=dt)
+            if a.shape != shape:
+                raise ValueError(f"bopt file: candidate {i}: {name} has the wrong shape")
+            blob.append(a.tobytes())
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class BurstOptFile:
+    """Reader of a burstopt result file (``bin/burstopt`` / ``python -m
+    peasoup_amd bopt``): ``len``, ``header``, ``candidate(i)``."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._buf = open(path, "rb").read()
+        if len(self._buf) < _BOPT_HEADER.size or self._buf[:8] != BOPT_MAGIC:
+            raise ValueError(f"{path}: not a burstopt result file")
+        vals = _BOPT_HEADER.unpack_from(self._buf, 0)[1:]
+        self.header: Dict = dict(zip(BOPT_HEADER_FIELDS, vals))
+        self._arrays = _bopt_arrays(self.header)
+        self._rec = _BOPT_CAND.size + sum(np.dtype(dt).itemsize * int(np.prod(sh)) for _, dt, sh in self._arrays)
+        if len(self._buf) != _BOPT_HEADER.size + self.header["ncand"] * self._rec:
+            raise ValueError(f"{path}: truncated burstopt result file")
+
+    def __len__(self) -> int:
+        return int(self.header["ncand"])
+
+    def candidate(self, i: int) -> Dict:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        o = _BOPT_HEADER.size + i * self._rec
+        out = dict(zip(_BOPT_SCALARS, _BOPT_CAND.unpack_from(self._buf, o)))
+        o += _BOPT_CAND.size
+        for name, dt, shape in self._arrays:
+            n = int(np.prod(shape))
+            out[name] = np.frombuffer(self._buf, dt, n, o).reshape(shape).copy()
+            o += n * np.dtype(dt).itemsize
+        return out
+
+
 # ---------------------------------------------------------------- RFI mask --
 RFI_MASK_MAGIC = b"PSMASK01"
 _MASK_HEADER = struct.Struct("<8s4I2Q4d")  # magic, nchans nblk nbits zero_dm, nsamps block, tsamp thresh chan_frac block_frac

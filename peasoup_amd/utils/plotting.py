@@ -162,6 +162,23 @@ def p_pdot_panel(rec: Dict) -> np.ndarray:
     return _opt_snr_plane(rec, rec["ppd"]).T.copy()
 
 
+def burst_dm_curve_panel(rec: Dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """(dms float64 [ndm], S/N float64 [ndm], dmf float64 [nfine], S/N float64
+    [nfine]) of a burstopt record: for every coarse DM row and every fine DM
+    row the best S/N (burstopt.hpp, step 4) over the bins and widths; the
+    coarse rows use their own off-pulse mean, the fine rows the waterfall's."""
+    dms = np.asarray(rec["dms"], dtype=np.float64)
+    dmf = np.asarray(rec["dmf"], dtype=np.float64)
+    curve = np.asarray(rec["curve"], dtype=np.float64)
+    ndm = dms.shape[0]
+    if not rec["v"] > 0:
+        return dms, np.zeros(ndm), dmf, np.zeros(dmf.shape[0])
+    w = (2.0 ** np.arange(curve.shape[0]))[:, None]
+    mbar = np.concatenate([np.asarray(rec["mbar_dmt"], dtype=np.float64), np.full(dmf.shape[0], float(rec["mbar_ds"]))])
+    snr = ((curve - w * mbar[None, :]) / np.sqrt(float(rec["v"]) * w)).max(axis=0)
+    return dms, snr[:ndm].copy(), dmf, snr[ndm:].copy()
+
+
 def _sizes(snr: np.ndarray) -> np.ndarray:
     s = np.asarray(snr, dtype=np.float64)
     if s.size == 0:

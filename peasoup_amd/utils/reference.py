@@ -1622,6 +1622,234 @@ def cube_optimise(cand: Dict, header: Dict, delays: np.ndarray, ndm: int = 64, n
     return rec
 
 
+# ---------------------------------------------------------------- burstopt --
+# The oracle of csrc/include/psoup/burstopt.hpp, written from its definition
+# in Python ints, int64 and float64.
+def burst_opt_nwidths(ntime: int) -> int:
+    nw, w = 1, 2
+    while w <= ntime // 2:
+        nw, w = nw + 1, w * 2
+    return nw
+
+
+def _bopt_off_pulse(ntime: int) -> np.ndarray:
+    k = np.arange(ntime)
+    return (k < ntime // 4) | (k >= ntime - ntime // 4)
+
+
+def _bopt_rows(sums, hits):
+    """Step 1 for the rows of one plane, in exact integers: (d, cnt, moff, v2) as object / int arrays."""
+    sums = np.asarray(sums, dtype=np.int64)
+    hits = np.asarray(hits, dtype=np.int64)
+    nrows, ntime = sums.shape
+    off = _bopt_off_pulse(ntime)
+    d = np.zeros((nrows, ntime), dtype=object)
+    cnt = np.zeros(nrows, dtype=np.int64)
+    moff = [0] * nrows
+    v2 = [0] * nrows
+    for r in range(nrows):
+        href = int(hits[r].max())
+        filled = hits[r] > 0
+        sel = filled & off
+        if href <= 0 or not sel.any():
+            continue
+        q = {int(k): (2 * int(sums[r, k]) * href + int(hits[r, k])) // (2 * int(hits[r, k])) for k in np.nonzero(filled)[0]}
+        cnt[r] = int(sel.sum())
+        base = sum(q[int(k)] for k in np.nonzero(sel)[0]) // int(cnt[r])
+        for k, v in q.items():
+            d[r, k] = v - base
+        moff[r] = sum(int(d[r, k]) for k in np.nonzero(sel)[0])
+        v2[r] = sum(int(d[r, k]) ** 2 for k in np.nonzero(sel)[0])
+    return d, cnt, moff, v2
+
+
+def burst_opt_prepare(cand: Dict, k: int = 0) -> Dict:
+    """Step 1 on a cutout dict (ds_sums, ds_hits, dmt_sums, dmt_hits; dm and
+    tscrunch where present): dict(d_ds int32 [nsub, ntime], d_dmt int32 [ndm,
+    ntime], cnt_ds, cnt_dmt int32, moff_ds, moff_dmt, v2_ds, v2_dmt int64, v,
+    mbar_ds, mbar_dmt float64 [ndm]).  Raises ValueError naming ``candidate
+    k`` where the definition refuses."""
+    ds_sums = np.asarray(cand["ds_sums"])
+    nsub, ntime = ds_sums.shape
+    who = f"burst opt: candidate {k} "
+    if ntime < 8:
+        raise ValueError(who + f"ntime = {ntime} is below 8")
+    dm = float(cand.get("dm", 0.0))
+    if not (math.isfinite(dm) and dm >= 0) or int(cand.get("tscrunch", 1)) < 1:
+        raise ValueError(who + "bad DM or tscrunch")
+    d_ds, cnt_ds, moff_ds, v2_ds = _bopt_rows(ds_sums, cand["ds_hits"])
+    nlive = int((cnt_ds > 0).sum())
+    if nlive == 0:
+        raise ValueError(who + "no waterfall row is live")
+    d_dmt, cnt_dmt, moff_dmt, v2_dmt = _bopt_rows(cand["dmt_sums"], cand["dmt_hits"])
+    max_ds = max(abs(int(d_ds.max())), abs(int(d_ds.min())))
+    max_dmt = max(abs(int(d_dmt.max())), abs(int(d_dmt.min())))
+    for d in (d_ds, d_dmt):
+        if int(d.max()) > 2 ** 31 - 1 or int(d.min()) < -2 ** 31:
+            raise ValueError(who + "a baseline-subtracted value does not fit int32")
+    if max_ds * nlive * (ntime // 2) >= 2 ** 31:
+        raise ValueError(who + "the waterfall's box sums do not fit int32")
+    if max_dmt * (ntime // 2) >= 2 ** 31:
+        raise ValueError(who + "the DM-time plane's box sums do not fit int32")
+    v = mbar = 0.0
+    for s in range(nsub):
+        if cnt_ds[s] > 0:
+            v = v + float(v2_ds[s]) / float(cnt_ds[s])
+            mbar = mbar + float(moff_ds[s]) / float(cnt_ds[s])
+    mbar_dmt = np.array([float(moff_dmt[j]) / float(cnt_dmt[j]) if cnt_dmt[j] > 0 else 0.0
+                         for j in range(len(cnt_dmt))], dtype=np.float64)
+    return {"d_ds": d_ds.astype(np.int32), "d_dmt": d_dmt.astype(np.int32), "cnt_ds": cnt_ds.astype(np.int32),
+            "cnt_dmt": cnt_dmt.astype(np.int32), "moff_ds": np.array(moff_ds, dtype=np.int64),
+            "moff_dmt": np.array(moff_dmt, dtype=np.int64), "v2_ds": np.array(v2_ds, dtype=np.int64),
+            "v2_dmt": np.array(v2_dmt, dtype=np.int64), "v": v, "mbar_ds": mbar, "mbar_dmt": mbar_dmt}
+
+
+def burst_opt_shifts(ntime: int, nsub: int, nchans: int, dm: float, f: int, dms, delays: np.ndarray, nfine: int = 65,
+                     fine_half_range: float = 0.0) -> Dict:
+    """Step 2: dict(dmf float32 [nfine], sf int32 [nfine, nsub])."""
+    if nfine < 1 or nfine > 257 or nfine % 2 == 0 or not fine_half_range >= 0:
+        raise ValueError("burst opt: nfine must be odd and in 1..257, fine_half_range non-negative")
+    dms = np.asarray(dms, dtype=np.float32)
+    ndm = len(dms)
+    half = float(fine_half_range)
+    if not half > 0:
+        half = 0.0 if ndm == 1 else float(dms[ndm // 2]) - float(dms[ndm // 2 - 1])
+    step = 0.0 if nfine == 1 else half / (nfine // 2)
+    dm0 = float(np.float32(dm))
+    dmf = np.array([max(0.0, dm0 + (kf - nfine // 2) * step) for kf in range(nfine)]).astype(np.float32)
+    delays = np.asarray(delays, dtype=np.float32)
+    sub_of = (np.arange(nchans, dtype=np.int64) * nsub) // nchans
+    sf = np.zeros((nfine, nsub), dtype=np.int32)
+    for s in range(nsub):
+        ch = np.nonzero(sub_of == s)[0]
+        dsub = 0.5 * (float(delays[ch[0]]) + float(delays[ch[-1]]))
+        for kf in range(nfine):
+            x = (float(dmf[kf]) - dm0) * dsub / float(int(f))
+            sf[kf, s] = int(min(max(np.rint(x), -float(ntime)), float(ntime)))
+    return {"dmf": dmf, "sf": sf}
+
+
+def burst_opt_profile(d_ds: np.ndarray, sf_row: np.ndarray) -> np.ndarray:
+    """P int64 [ntime] of one fine row: terms outside the window are 0."""
+    d_ds = np.asarray(d_ds).astype(np.int64)
+    nsub, ntime = d_ds.shape
+    k = np.arange(ntime)
+    prof = np.zeros(ntime, dtype=np.int64)
+    for s in range(nsub):
+        x = k + int(sf_row[s])
+        ok = (x >= 0) & (x < ntime)
+        prof[ok] += d_ds[s, x[ok]]
+    return prof
+
+
+def burst_opt_search(d_ds: np.ndarray, d_dmt: np.ndarray, sf: np.ndarray) -> Dict:
+    """Step 3 from the definition: dict(best_val, best_idx int32 [2, nw] (the
+    coarse plane first); curve, curve_bin int32 [nw, ndm + nfine])."""
+    d_dmt = np.asarray(d_dmt).astype(np.int64)
+    sf = np.asarray(sf)
+    ndm, ntime = d_dmt.shape
+    nfine = sf.shape[0]
+    nw = burst_opt_nwidths(ntime)
+    P = np.concatenate([d_dmt, np.stack([burst_opt_profile(d_ds, sf[kf]) for kf in range(nfine)])], axis=0)
+    lowest = -2 ** 62
+    csum = np.concatenate([np.zeros((P.shape[0], 1), dtype=np.int64), np.cumsum(P, axis=1)], axis=1)
+    curve = np.zeros((nw, ndm + nfine), dtype=np.int64)
+    curve_bin = np.zeros((nw, ndm + nfine), dtype=np.int64)
+    best_val = np.zeros((2, nw), dtype=np.int64)
+    best_idx = np.zeros((2, nw), dtype=np.int64)
+    for kw in range(nw):
+        w = 1 << kw
+        S = np.full((ndm + nfine, ntime), lowest, dtype=np.int64)
+        S[:, :ntime - w + 1] = csum[:, w:] - csum[:, :ntime - w + 1]
+        assert np.abs(S[:, :ntime - w + 1]).max(initial=0) < 2 ** 31
+        curve[kw] = S.max(axis=1)
+        curve_bin[kw] = S.argmax(axis=1)  # the first occurrence
+        for plane, rows in ((0, slice(0, ndm)), (1, slice(ndm, ndm + nfine))):
+            flat = S[rows].reshape(-1)
+            best_val[plane, kw] = flat.max()
+            best_idx[plane, kw] = int(flat.argmax())
+    return {"best_val": best_val.astype(np.int32), "best_idx": best_idx.astype(np.int32),
+            "curve": curve.astype(np.int32), "curve_bin": curve_bin.astype(np.int32)}
+
+
+def burst_opt_snr(s: float, w: int, mbar: float, v: float) -> float:
+    if not v > 0:
+        return 0.0
+    return (float(s) - w * float(mbar)) / math.sqrt(v * w)
+
+
+def burst_opt_finish(cand: Dict, prep: Dict, shifts: Dict, found: Dict) -> Dict:
+    """Step 4: the record of one candidate (the search outputs included).
+    ``cand`` needs tscrunch, t0 and dms."""
+    d_ds = np.asarray(prep["d_ds"]).astype(np.int64)
+    nsub, ntime = d_ds.shape
+    dms = np.asarray(cand["dms"], dtype=np.float32)
+    ndm = len(dms)
+    nw = burst_opt_nwidths(ntime)
+    f, t0 = int(cand["tscrunch"]), int(cand["t0"])
+    v = prep["v"]
+
+    def best_of(vals, mbars):
+        best, which = 0.0, 0
+        for k in range(nw):
+            s = burst_opt_snr(float(int(vals[k])), 1 << k, float(mbars[k]), v)
+            if k == 0 or s > best:
+                best, which = s, k
+        return best, which
+
+    bv, bi = np.asarray(found["best_val"]), np.asarray(found["best_idx"])
+    curve = np.asarray(found["curve"])
+    snr_coarse, kc = best_of(bv[0], [prep["mbar_dmt"][int(bi[0, k]) // ntime] for k in range(nw)])
+    coarse_row, coarse_bin = int(bi[0, kc]) // ntime, int(bi[0, kc]) % ntime
+    snr_in, _ = best_of(curve[:, ndm // 2], [prep["mbar_dmt"][ndm // 2]] * nw)
+    flags = 0
+    if float(dms[0]) == 0.0:
+        snr_dm0, _ = best_of(curve[:, 0], [prep["mbar_dmt"][0]] * nw)
+    else:
+        snr_dm0, flags = 0.0, 1
+    snr, kb = best_of(bv[1], [prep["mbar_ds"]] * nw)
+    w = 1 << kb
+    opt_kf, opt_bin = int(bi[1, kb]) // ntime, int(bi[1, kb]) % ntime
+    sf = np.asarray(shifts["sf"])[opt_kf]
+    band = np.zeros(nsub, dtype=np.int64)
+    nlive = npos = 0
+    for s in range(nsub):
+        if prep["cnt_ds"][s] == 0:
+            continue
+        x = opt_bin + np.arange(w) + int(sf[s])
+        ok = (x >= 0) & (x < ntime)
+        band[s] = int(d_ds[s, x[ok]].sum())
+        nlive += 1
+        if float(int(band[s])) - w * (float(int(prep["moff_ds"][s])) / float(int(prep["cnt_ds"][s]))) > 0:
+            npos += 1
+    out = {k: np.asarray(a).copy() for k, a in found.items()}
+    out.update(snr=snr, snr_coarse=snr_coarse, snr_in=snr_in, snr_dm0=snr_dm0,
+               frac_pos=float(npos) / float(nlive) if nlive else 0.0, v=v, mbar_ds=prep["mbar_ds"],
+               opt_sample=t0 + opt_bin * f, opt_dm=float(shifts["dmf"][opt_kf]), coarse_dm=float(dms[coarse_row]),
+               opt_width=w * f, opt_kf=opt_kf, opt_bin=opt_bin, coarse_row=coarse_row, coarse_width=(1 << kc) * f,
+               coarse_bin=coarse_bin, flags=flags, dms=dms.copy(), dmf=np.asarray(shifts["dmf"]).copy(),
+               mbar_dmt=np.asarray(prep["mbar_dmt"], dtype=np.float64).copy(), band=band.astype(np.int32),
+               profile=burst_opt_profile(d_ds, sf).astype(np.int32))
+    return out
+
+
+def burst_optimise(cand: Dict, header: Dict, delays: np.ndarray, nfine: int = 65, fine_half_range: float = 0.0,
+                   k: int = 0) -> Dict:
+    """The whole chain on one cutout dict (``BurstCubeFile.candidate``'s keys,
+    or reference.burst_cube's plus sample, width, dm) of a burst-cutout file
+    with ``header`` (nchans): burst_opt_finish's record plus sample, width,
+    tscrunch, t0, dm and cand_snr."""
+    prep = burst_opt_prepare(cand, k)
+    nsub, ntime = prep["d_ds"].shape
+    sh = burst_opt_shifts(ntime, nsub, int(header["nchans"]), float(cand["dm"]), int(cand["tscrunch"]), cand["dms"],
+                          delays, nfine, fine_half_range)
+    found = burst_opt_search(prep["d_ds"], prep["d_dmt"], sh["sf"])
+    rec = burst_opt_finish(cand, prep, sh, found)
+    rec.update(sample=int(cand["sample"]), width=int(cand["width"]), tscrunch=int(cand["tscrunch"]),
+               t0=int(cand["t0"]), dm=float(np.float32(cand["dm"])), cand_snr=float(np.float32(cand.get("snr", 0.0))))
+    return rec
+
+
 # -------------------------------------------------------------- filscrunch --
 # The oracle of csrc/include/psoup/scrunch.hpp, written from its definition.
 SCRUNCH_BLOCK = 4096
