@@ -127,6 +127,7 @@ void bind_opt(py::module_& m);   // bind_opt.cpp
 void bind_scrunch(py::module_& m);  // bind_scrunch.cpp
 void bind_digi(py::module_& m);     // bind_digi.cpp
 void bind_fits(py::module_& m);     // bind_fits.cpp
+void bind_inject(py::module_& m);   // bind_inject.cpp
 void bind_bopt(py::module_& m);     // bind_bopt.cpp
 
 PYBIND11_MODULE(_C, m) {
@@ -706,6 +707,7 @@ PYBIND11_MODULE(_C, m) {
   bind_scrunch(m);
   bind_digi(m);
   bind_fits(m);
+  bind_inject(m);
   bind_bopt(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");

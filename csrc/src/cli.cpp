@@ -3,6 +3,7 @@
 #include "psoup/burstopt.hpp"
 #include "psoup/cubeopt.hpp"
 #include "psoup/digi.hpp"
+#include "psoup/inject.hpp"
 #include "psoup/psrfits.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
@@ -697,6 +698,48 @@ bool parse_digi_cmdline(DigiCmdLineOptions& a, const std::vector<std::string>& a
   }
   if (a.rescale_blocks < 0) {
     std::cerr << "Error: --rescale_blocks must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_inject_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_filinject.fil", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_inject_cmdline(InjectCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_inject_output_filename();
+  std::string seed = "0";
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil of 1, 2, 4 or 8 bits)", a.infilename, true),
+      val_s("o", "outfilename", "The filterbank with the signals added (same width and header)", a.outfilename),
+      val_s("", "injfile", "Signals: 'pulsar period_s dm amp [duty acc phase alpha]' or 'burst time_s dm amp "
+                           "[width_s alpha]' per line",
+            a.injfilename, true),
+      val_s("k", "killfile", "Channel mask file: killed channels are left untouched", a.killfilename),
+      val_s("", "seed", "Seed of the dither (a non-negative integer)", seed),
+      val_s("", "units", "sigma: amp in units of each channel's noise sigma; level: in raw levels", a.units),
+      sw("", "no_smear", "Do not widen the pulses by the intra-channel DM smearing", a.no_smear),
+      val_s("", "truth_out", "Truth file: one line per signal with npulses, peak level and expected S/N",
+            a.truthfilename),
+      sw("v", "verbose", "verbose mode: print nclip, the live count and the touched samples per signal", a.verbose),
+  };
+  if (!run_parser(specs, argv, "Peasoup filinject extension - inject dispersed pulsars and bursts into a filterbank",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  bool digits = !seed.empty() && seed.size() <= 19;
+  for (char c : seed) digits = digits && std::isdigit(static_cast<unsigned char>(c));
+  if (!digits) {
+    std::cerr << "Error: --seed must be a non-negative integer below 10^19" << std::endl;
+    return false;
+  }
+  a.seed = std::stoull(seed);
+  if (a.units != "sigma" && a.units != "level") {
+    std::cerr << "Error: --units must be sigma or level" << std::endl;
     return false;
   }
   return true;

@@ -8,7 +8,8 @@ on fold cubes, ``python -m peasoup_amd bopt [burstopt flags]`` for the DM / widt
 cutouts, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, ``python -m peasoup_amd
 scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``python -m peasoup_amd digi
 [fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank, ``python -m peasoup_amd
-fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file) -- the peasoup CLI as a
+fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file, ``python -m peasoup_amd inject
+[filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -90,6 +91,8 @@ def main(argv=None) -> int:
         return _main_digi(["fildigi"] + argv[2:])
     if len(argv) > 1 and argv[1] == "fits":
         return _main_fits(["fits2fil"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "inject":
+        return _main_inject(["filinject"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -315,6 +318,29 @@ def _main_fits(argv) -> int:
               f"{res['nsamps']} samples x {res['nchans']} channels, nbad {int(res['nbad'].sum())}, nclip "
               f"{res['nclip']}, {res['nlive']} of {res['nchans']} channels live, gains {res['gain_min']:g} to "
               f"{res['gain_max']:g}")
+    return 0
+
+
+def _main_inject(argv) -> int:
+    from . import _C
+    from .models.inject import inject_filterbank
+
+    ok, exit_now, args = _C.parse_inject_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = inject_filterbank(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("inject", e)
+    if res is not None and args.verbose:
+        print(f"filinject: {res['nsamps']} samples x {res['nchans']} channels, {res['nsig']} signals, nclip "
+              f"{res['nclip']}, {res['nlive']} of {res['nchans']} channels live, {res['chunks']} chunk(s)")
+        for i, (s, t) in enumerate(zip(res["signals"], res["truth"])):
+            print(f"  signal {i} ({s.kind}): {int(res['touched'][i])} samples touched, {t[0]} pulses, peak {t[1]:g} "
+                  f"levels, expected S/N {t[2]:g}")
     return 0
 
 

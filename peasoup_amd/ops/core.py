@@ -1043,3 +1043,77 @@ def fits_digitise(file_bytes, sigma_out: float = 16.0, scale: str = "channel", r
     res["launches"] = int(dig.launches)
     res["chunk_samples"] = int(dig.chunk_samples)
     return y, res
+
+
+# --------------------------------------------------------------- filinject --
+# csrc/include/psoup/inject.hpp (definition), csrc/kernels/inject.hip.
+def inject_tile() -> int:
+    """Samples per workgroup of the inject kernel."""
+    return int(_C.inject_tile())
+
+
+def _inject_signals(signals) -> list:
+    """PulsarSpec / BurstSpec (utils.synthetic) or ``_C.InjectSignal`` -> ``_C.InjectSignal``."""
+    out = []
+    for s in signals:
+        if isinstance(s, _C.InjectSignal):
+            out.append(s)
+        elif hasattr(s, "period"):
+            out.append(_C.InjectSignal("pulsar", float(s.period), float(s.dm), float(s.amplitude), float(s.duty),
+                                       float(s.accel), float(s.phase), float(getattr(s, "alpha", 0.0))))
+        else:
+            out.append(_C.InjectSignal("burst", float(s.time), float(s.dm), float(s.amplitude), float(s.width), 0.0,
+                                       0.0, float(getattr(s, "alpha", 0.0))))
+    return out
+
+
+def inject_tables(signals, header: Dict, nsamps: int, unit, smear: bool = True) -> Dict:
+    """The host tables of the definition (no GPU): sigc, delay, inv_w, w, A_q,
+    T, tsamp, nlive for ``signals`` in the filterbank ``header`` describes;
+    ``unit`` [nchans] is each channel's sigma (or 1), 0 where untouched.
+    Equals ``utils.reference.inject_tables``."""
+    return _C.inject_tables(_inject_signals(signals), int(header["nchans"]), int(header["nbits"]), int(nsamps),
+                            float(header["tsamp"]), float(header["fch1"]), float(header["foff"]),
+                            np.asarray(unit, dtype=np.float64), bool(smear))
+
+
+def inject(chan_major: torch.Tensor, nsamps: int, nbits: int, tables: Dict, seed: int = 0, t0: int = 0,
+           bias: int = 0):
+    """The inject kernel alone, in place on int8 rows [nchans, stride] (raw
+    sample = stored value + ``bias``) that hold the file's samples from ``t0``
+    on, with explicit ``tables`` (as ``inject_tables`` or the oracle's).
+    Returns (the tensor, nclip, touched [nsig]); equals
+    ``utils.reference.inject_apply``."""
+    nchans, stride = _check_rows(chan_major, "chan_major")
+    if int(tables["delay"].shape[1]) != nchans:
+        raise ValueError("the tables do not fit the rows")
+    if int(nsamps) > stride:
+        raise ValueError("nsamps exceeds the stride")
+    nclip, touched = _C.inject_raw(chan_major.data_ptr(), stride, int(nsamps), int(nbits), int(bias), int(t0),
+                                   np.asarray(tables["sigc"], dtype=np.float64), float(tables["tsamp"]),
+                                   np.asarray(tables["delay"], dtype=np.float64),
+                                   np.asarray(tables["inv_w"], dtype=np.float64),
+                                   np.asarray(tables["A_q"], dtype=np.uint32),
+                                   np.asarray(tables["T"], dtype=np.uint16), int(seed), _s())
+    return chan_major, int(nclip), touched
+
+
+def inject_filterbank_bytes(packed: np.ndarray, header: Dict, nsamps: int, signals, killmask=None, seed: int = 0,
+                            units: str = "sigma", smear: bool = True, budget_bytes: Optional[int] = None):
+    """filinject on the packed bytes of a filterbank's data block (a NumPy
+    uint8 array on the host): the native ``Injector`` in time chunks
+    (statistics pass, host tables, injection pass).  ``signals``: PulsarSpec /
+    BurstSpec.  Returns (packed bytes out, result dict with nclip, touched,
+    sigma, truth, chunks and the tables).  Everything is validated before the
+    first launch."""
+    if units not in ("sigma", "level"):
+        raise ValueError("inject: units must be sigma or level")
+    kill = [] if killmask is None else [int(k) for k in killmask]
+    kw = {} if budget_bytes is None else {"budget_bytes": int(budget_bytes)}
+    inj = _C.Injector(np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1), int(header["nchans"]),
+                      int(header["nbits"]), int(nsamps), float(header["tsamp"]), float(header["fch1"]),
+                      float(header["foff"]), _inject_signals(signals), kill, units == "sigma", bool(smear), int(seed),
+                      _s(), **kw)
+    y, res = inj.run()
+    res["chunk_samples"] = int(inj.chunk_samples)
+    return y, res

@@ -2361,3 +2361,290 @@ def fits_filterbank(infile, outfile: Optional[str] = None, sigma_out: float = 16
             fo.write("".join("1\n" if v else "0\n" for v in alive))
     return dict(sums, **sc, x=x, y=y, nclip=nclip, flip=flip, killmask=[int(v) for v in alive], header=hdr,
                 header_bytes=head, slots=slots, pols=pols, z=f["z"], rows=nrows)
+
+
+# --------------------------------------------------------------- filinject --
+# The oracle of csrc/include/psoup/inject.hpp, written from its definition:
+# uint64 / float64 NumPy, one correctly rounded operation at a time.
+INJECT_BLOCK = 4096
+INJECT_STEPS = 256
+INJECT_TABLE_LEN = 6 * INJECT_STEPS + 1
+INJECT_MAX_SIGNALS = 64
+_INJ_GOLDEN = 0x9E3779B97F4A7C15
+_INJ_M1 = 0xBF58476D1CE4E5B9
+_INJ_M2 = 0x94D049BB133111EB
+_INJ_MASK = (1 << 64) - 1
+
+
+def inject_hash(seed: int, c: int, t: int) -> int:
+    """The dither's 64-bit draw z of sample (c, t), in Python integers."""
+    z = ((int(seed) + 1) * _INJ_GOLDEN + ((int(c) << 40) | int(t))) & _INJ_MASK
+    z = ((z ^ (z >> 30)) * _INJ_M1) & _INJ_MASK
+    z = ((z ^ (z >> 27)) * _INJ_M2) & _INJ_MASK
+    return z ^ (z >> 31)
+
+
+def inject_draws(seed: int, c: int, t: np.ndarray) -> np.ndarray:
+    """z >> 33 (31 bits) for the absolute sample indices ``t`` (uint64) of channel c."""
+    base = np.uint64(((int(seed) + 1) * _INJ_GOLDEN + (int(c) << 40)) & _INJ_MASK)
+    with np.errstate(over="ignore"):
+        z = base + np.asarray(t, dtype=np.uint64)   # (c << 40) | t == (c << 40) + t for t < 2^40
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(_INJ_M1)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(_INJ_M2)
+        z = z ^ (z >> np.uint64(31))
+    return z >> np.uint64(33)
+
+
+def inject_profile_table() -> np.ndarray:
+    k = np.arange(INJECT_TABLE_LEN, dtype=np.float64)
+    return np.rint(32768.0 * np.exp(-(k * k) / (2.0 * INJECT_STEPS * INJECT_STEPS))).astype(np.uint16)
+
+
+def inject_check_signals(signals) -> None:
+    """The refusals of the definition, by name (ValueError)."""
+    if len(signals) == 0:
+        raise ValueError("inject: no signal to inject")
+    if len(signals) > INJECT_MAX_SIGNALS:
+        raise ValueError("inject: more than 64 signals")
+    for i, s in enumerate(signals):
+        burst = not hasattr(s, "period")
+        vals = [s.dm, s.amplitude, getattr(s, "alpha", 0.0)]
+        vals += [s.time, s.width] if burst else [s.period, s.duty, s.accel, s.phase]
+        if not all(math.isfinite(float(v)) for v in vals):
+            raise ValueError(f"inject: signal {i}: a value is not finite")
+        if s.amplitude < 0:
+            raise ValueError(f"inject: signal {i}: amp must not be negative")
+        if s.dm < 0:
+            raise ValueError(f"inject: signal {i}: dm must not be negative")
+        if burst:
+            if not s.width > 0:
+                raise ValueError(f"inject: signal {i}: width must be positive")
+        else:
+            if not s.period > 0:
+                raise ValueError(f"inject: signal {i}: period must be positive")
+            if not s.duty > 0:
+                raise ValueError(f"inject: signal {i}: duty must be positive")
+            if s.duty > 1:
+                raise ValueError(f"inject: signal {i}: duty must not exceed 1")
+
+
+def inject_parse(text: str) -> List:
+    """The injection file's text -> PulsarSpec / BurstSpec list (checked)."""
+    from .synthetic import BurstSpec, PulsarSpec
+
+    out = []
+    for n, line in enumerate(text.splitlines(), 1):
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        if tok[0] not in ("pulsar", "burst"):
+            raise ValueError(f"inject: line {n}: unknown kind '{tok[0]}' (pulsar or burst)")
+        if len(tok) < 4:
+            raise ValueError(f"inject: line {n}: {tok[0]} needs at least three columns")
+        if len(tok) > (8 if tok[0] == "pulsar" else 6):
+            raise ValueError(f"inject: line {n}: too many columns for a {tok[0]}")
+        try:
+            v = [float(x) for x in tok[1:]]
+        except ValueError:
+            raise ValueError(f"inject: line {n}: cannot read a column") from None
+        if tok[0] == "pulsar":
+            v += [0.05, 0.0, 0.0, 0.0][len(v) - 3:]
+            out.append(PulsarSpec(period=v[0], dm=v[1], amplitude=v[2], duty=v[3], accel=v[4], phase=v[5], alpha=v[6]))
+        else:
+            v += [0.005, 0.0][len(v) - 3:]
+            out.append(BurstSpec(time=v[0], dm=v[1], amplitude=v[2], width=v[3], alpha=v[4]))
+        if len(out) > INJECT_MAX_SIGNALS:
+            raise ValueError("inject: more than 64 signals")
+    inject_check_signals(out)
+    return out
+
+
+def inject_sigma(S1: np.ndarray, S2: np.ndarray, nsamps: int) -> np.ndarray:
+    """sigma[c] from the block sums [nchans, nblk] of blocks of 4096 samples:
+    the square root of the median of (n S2 - S1^2) / n^2 over the full blocks
+    (a shorter file: its one short block)."""
+    S1 = np.asarray(S1)
+    S2 = np.asarray(S2)
+    nchans = S1.shape[0]
+    nfull = int(nsamps) // INJECT_BLOCK
+    n = INJECT_BLOCK if nfull else int(nsamps)
+    nuse = nfull if nfull else 1
+    sigma = np.zeros(nchans, dtype=np.float64)
+    for c in range(nchans):
+        v = [float(n * int(S2[c, b]) - int(S1[c, b]) ** 2) / float(n * n) for b in range(nuse)]
+        sigma[c] = math.sqrt(float(np.median(np.array(v, dtype=np.float64))))
+    return sigma
+
+
+def inject_unit(sigma, killmask, nchans: int) -> np.ndarray:
+    unit = np.ones(nchans, dtype=np.float64) if sigma is None else np.array(sigma, dtype=np.float64)
+    if killmask is not None and len(killmask):
+        unit[np.asarray(killmask) == 0] = 0.0
+    return unit
+
+
+def inject_tables(signals, header: Dict, unit, smear: bool = True) -> Dict:
+    """The per-channel tables of the definition for PulsarSpec / BurstSpec
+    ``signals``: sigc [nsig, 4], delay, inv_w, w [nsig, nchans] float64, A_q
+    [nsig, nchans] uint32, T [1537] uint16, tsamp, nlive."""
+    inject_check_signals(signals)
+    nchans = int(header["nchans"])
+    tsamp, fch1, foff = float(header["tsamp"]), float(header["fch1"]), float(header["foff"])
+    unit = np.asarray(unit, dtype=np.float64)
+    ns = len(signals)
+    D = delay_table(nchans, tsamp, fch1, foff).astype(np.float64)
+    f_c = fch1 + np.arange(nchans, dtype=np.float64) * foff
+    f_mid = fch1 + foff * float(nchans - 1) / 2.0
+    sigc = np.zeros((ns, 4), dtype=np.float64)
+    delay = np.zeros((ns, nchans), dtype=np.float64)
+    w = np.zeros((ns, nchans), dtype=np.float64)
+    A_q = np.zeros((ns, nchans), dtype=np.uint32)
+    for s, sg in enumerate(signals):
+        burst = not hasattr(sg, "period")
+        alpha = float(getattr(sg, "alpha", 0.0))
+        if burst:
+            sigc[s] = (1.0, float(sg.time) / tsamp, 0.0, 0.0)
+            f0 = 0.0
+            w0 = float(sg.width) / tsamp / 2.3548
+        else:
+            f0 = 1.0 / float(sg.period)
+            sigc[s] = (0.0, float(sg.accel) / (2.0 * C_LIGHT), f0, float(sg.phase))
+            w0 = float(sg.duty) / 2.3548
+        delay[s] = float(sg.dm) * D
+        if smear:
+            fg = f_c / 1000.0
+            sm_s = 8.3e-6 * float(sg.dm) * abs(foff) / (fg * fg * fg)
+            sm = sm_s / tsamp if burst else sm_s * f0
+            w[s] = np.sqrt(w0 * w0 + sm * sm)
+        else:
+            w[s] = w0
+        a = float(sg.amplitude) * unit
+        if alpha != 0.0:
+            a = a * np.power(f_c / f_mid, alpha)
+        a = a * (w0 / w[s])
+        q = np.rint(65536.0 * a)
+        if np.any(q >= 16777216.0):
+            raise ValueError(f"inject: signal {s}: the amplitude reaches 256 levels (A_q >= 2^24)")
+        A_q[s] = q.astype(np.uint32)
+    return {"nsig": ns, "nchans": nchans, "tsamp": tsamp, "sigc": sigc, "delay": delay, "inv_w": float(INJECT_STEPS) / w,
+            "w": w, "A_q": A_q, "T": inject_profile_table(), "nlive": int(np.count_nonzero(unit > 0))}
+
+
+def inject_expected(tab: Dict, c: int, t: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """E (uint64, Q31 levels) of channel c at the absolute samples ``t``
+    (uint64), and the touched count of every signal there."""
+    tf = np.asarray(t, dtype=np.uint64).astype(np.float64)
+    E = np.zeros(tf.shape, dtype=np.uint64)
+    T = tab["T"].astype(np.uint64)
+    tsamp = float(tab["tsamp"])
+    touched = np.zeros(tab["nsig"], dtype=np.uint64)
+    for s in range(tab["nsig"]):
+        a = int(tab["A_q"][s, c])
+        if a == 0:
+            continue
+        kind, k1, k2, k3 = (float(v) for v in tab["sigc"][s])
+        x = tf - float(tab["delay"][s, c])
+        if kind != 0.0:
+            d = np.abs(x - k1)
+        else:
+            te = x * tsamp
+            ph = (te - (k1 * te) * te) * k2 + k3
+            ph = ph - np.floor(ph)
+            d = np.minimum(ph, 1.0 - ph)
+        u = d * float(tab["inv_w"][s, c])
+        hit = u < (INJECT_TABLE_LEN - 1) + 0.5
+        k = np.rint(u[hit]).astype(np.int64)
+        E[hit] += np.uint64(a) * T[k]
+        touched[s] = np.count_nonzero(hit)
+    return E, touched
+
+
+def inject_apply(values: np.ndarray, tab: Dict, nbits: int, seed: int = 0, t0: int = 0):
+    """The per-sample step on raw samples ``values`` [nchans, nsamps] holding
+    the file's samples from ``t0`` on.  Returns (out uint8, nclip, touched
+    uint64 [nsig])."""
+    x = np.asarray(values)
+    nchans, nsamps = x.shape
+    L = (1 << int(nbits)) - 1
+    t = np.uint64(t0) + np.arange(nsamps, dtype=np.uint64)
+    out = np.empty((nchans, nsamps), dtype=np.uint8)
+    nclip = 0
+    touched = np.zeros(tab["nsig"], dtype=np.uint64)
+    for c in range(nchans):
+        E, tc = inject_expected(tab, c, t)
+        touched += tc
+        add = (E + inject_draws(seed, c, t)) >> np.uint64(31)
+        y = x[c].astype(np.uint64) + add
+        nclip += int(np.count_nonzero(y > L))
+        out[c] = np.minimum(y, np.uint64(L)).astype(np.uint8)
+    return out, nclip, touched
+
+
+def inject_truth(signals, tab: Dict, header: Dict, nsamps: int, unit, sigma) -> List[Tuple[int, float, float]]:
+    """(npulses, peak, snr) per signal; sigma None (level units): snr 0."""
+    tsamp = float(header["tsamp"])
+    unit = np.asarray(unit, dtype=np.float64)
+    live = unit > 0
+    out = []
+    for s, sg in enumerate(signals):
+        kind, k1, k2, k3 = (float(v) for v in tab["sigc"][s])
+        if kind != 0.0:
+            npulses = 1 if 0 <= k1 < float(nsamps) else 0
+        else:
+            te = float(nsamps - 1) * tsamp
+            n = math.floor((te - (k1 * te) * te) * k2 + k3) - math.ceil(k3) + 1
+            npulses = max(0, int(n))
+        a = tab["A_q"][s].astype(np.float64) / 65536.0
+        peak = float(np.sum(a[live]) / np.count_nonzero(live)) if np.any(live) else 0.0
+        snr = 0.0
+        if sigma is not None:
+            sg_ = np.asarray(sigma, dtype=np.float64)
+            ok = live & (sg_ > 0)
+            ws = tab["w"][s] if kind != 0.0 else tab["w"][s] * float(sg.period) / tsamp
+            r = a[ok] / sg_[ok]
+            snr = math.sqrt(float(np.sum(((r * r) * float(npulses)) * (ws[ok] * math.sqrt(math.pi)))))
+        out.append((npulses, peak, snr))
+    return out
+
+
+def inject_filterbank(infile: str, outfile: Optional[str], signals, killmask=None, seed: int = 0, units: str = "sigma",
+                      smear: bool = True) -> Dict:
+    """The whole tool on the CPU: reads ``infile``, adds ``signals`` (a list of
+    PulsarSpec / BurstSpec, or the injection file's text) and writes
+    ``outfile`` (when given) with the header bytes verbatim.  Returns packed
+    (the data block's bytes), values [nsamps, nchans], nclip, touched, sigma,
+    the tables and truth."""
+    import os
+
+    from .sigproc import pack_samples, read_filterbank
+
+    if units not in ("sigma", "level"):
+        raise ValueError("inject: units must be sigma or level")
+    if isinstance(signals, str):
+        signals = inject_parse(signals)
+    fb = read_filterbank(infile)
+    hdr = fb.header
+    nsamps, nchans = fb.data.shape
+    nbits = int(hdr["nbits"])
+    if nsamps < 1:
+        raise ValueError("inject: the input is shorter than one sample")
+    rows = np.ascontiguousarray(fb.data.T)
+    sigma = None
+    if units == "sigma":
+        S1, S2 = rfi_block_sums(rows, INJECT_BLOCK)
+        sigma = inject_sigma(S1, S2, nsamps)
+    unit = inject_unit(sigma, killmask, nchans)
+    tab = inject_tables(signals, hdr, unit, smear)
+    out, nclip, touched = inject_apply(rows, tab, nbits, seed, 0)
+    values = np.ascontiguousarray(out.T)
+    packed = pack_samples(values, nbits)
+    if outfile:
+        with open(infile, "rb") as f:
+            head = f.read(int(hdr["size"]))
+        tmp = outfile + ".tmp"
+        with open(tmp, "wb") as fo:
+            fo.write(head)
+            fo.write(packed.tobytes())
+        os.replace(tmp, outfile)
+    return {"packed": packed, "values": values, "nclip": nclip, "touched": touched, "sigma": sigma, "unit": unit,
+            "tables": tab, "truth": inject_truth(signals, tab, hdr, nsamps, unit, sigma)}

@@ -26,6 +26,7 @@ class PulsarSpec:
     amplitude: float = 1.0      # peak in units of the per-channel noise sigma
     accel: float = 0.0          # m/s^2
     phase: float = 0.0
+    alpha: float = 0.0          # spectral index about the band centre (filinject only)
 
 
 @dataclass
@@ -35,6 +36,7 @@ class BurstSpec:
     dm: float = 30.0            # pc cm^-3
     width: float = 5e-3         # FWHM (s)
     amplitude: float = 1.0      # peak in units of the per-channel noise sigma
+    alpha: float = 0.0          # spectral index about the band centre (filinject only)
 
 
 @dataclass
