@@ -129,6 +129,7 @@ void bind_digi(py::module_& m);     // bind_digi.cpp
 void bind_fits(py::module_& m);     // bind_fits.cpp
 void bind_inject(py::module_& m);   // bind_inject.cpp
 void bind_bopt(py::module_& m);     // bind_bopt.cpp
+void bind_jerk(py::module_& m);     // bind_jerk.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -709,6 +710,7 @@ PYBIND11_MODULE(_C, m) {
   bind_fits(m);
   bind_inject(m);
   bind_bopt(m);
+  bind_jerk(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -9,7 +9,8 @@ cutouts, ``python -m peasoup_amd clean [rficlean flags]`` for the RFI excision, 
 scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``python -m peasoup_amd digi
 [fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank, ``python -m peasoup_amd
 fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file, ``python -m peasoup_amd inject
-[filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank) -- the peasoup CLI as a
+[filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank, ``python -m peasoup_amd jerk
+[jerksearch flags]`` for the acceleration search repeated over jerk trials) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -93,6 +94,8 @@ def main(argv=None) -> int:
         return _main_fits(["fits2fil"] + argv[2:])
     if len(argv) > 1 and argv[1] == "inject":
         return _main_inject(["filinject"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "jerk":
+        return _main_jerk(["jerksearch"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -341,6 +344,26 @@ def _main_inject(argv) -> int:
         for i, (s, t) in enumerate(zip(res["signals"], res["truth"])):
             print(f"  signal {i} ({s.kind}): {int(res['touched'][i])} samples touched, {t[0]} pulses, peak {t[1]:g} "
                   f"levels, expected S/N {t[2]:g}")
+    return 0
+
+
+def _main_jerk(argv) -> int:
+    from . import _C
+    from .models.jerk import run_jerk_search
+
+    ok, exit_now, args = _C.parse_jerk_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = run_jerk_search(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("jerk", e)
+    if res is not None and args.search.verbose:
+        print(f"jerksearch: {len(res.candidates)} candidates from {res.jerk_trials} DM-jerk trials "
+              f"({res.accel_trials} acceleration trials) to {args.outfilename}")
     return 0
 
 

@@ -1117,3 +1117,40 @@ def inject_filterbank_bytes(packed: np.ndarray, header: Dict, nsamps: int, signa
     y, res = inj.run()
     res["chunk_samples"] = int(inj.chunk_samples)
     return y, res
+
+
+# ------------------------------------------------------------------ jerk ----
+def jerk_factors(jerks: Sequence[float], tsamp: float) -> np.ndarray:
+    """The definition's jf (float64) of jerk trials in m/s^3 (taken as float32,
+    like ``tsamp``): jerk tsamp^2 / (6 c).  Equals ``utils.reference.jerk_factor``."""
+    return np.array([_C.jerk_factor(float(np.float32(j)), float(np.float32(tsamp))) for j in jerks], dtype=np.float64)
+
+
+def jerk_resample(trials: torch.Tensor, n: int, jerks: Sequence[float], tsamp: float, nrow: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None, factors=None) -> torch.Tensor:
+    """The jerk_resample kernel: uint8 rows ``trials`` [nrows, row_stride], of
+    which the first ``nrow`` samples (default: all) are the row and the first
+    ``n`` the resampled span, re-indexed at each jerk trial.  Returns ``out``
+    [nrows, K, out_stride] (allocated as [nrows, K, nrow] when not given) with
+    out[r, k, :nrow] the definition's y; bytes past nrow are not written.
+    ``factors`` gives the jerk factors themselves instead of ``jerks`` and
+    ``tsamp``.  Equals ``utils.reference.jerk_resample`` byte for byte."""
+    _check(trials, torch.uint8, "trials")
+    if trials.dim() != 2:
+        raise ValueError("trials must be [nrows, row_stride]")
+    nrows, row_stride = int(trials.shape[0]), int(trials.shape[1])
+    nrow = row_stride if nrow is None else int(nrow)
+    jf = jerk_factors(jerks, tsamp) if factors is None else np.asarray(factors, dtype=np.float64).reshape(-1)
+    K = int(jf.size)
+    if out is None:
+        out = torch.empty((nrows, K, nrow), dtype=torch.uint8, device=trials.device)
+    _check(out, torch.uint8, "out")
+    if out.dim() != 3 or int(out.shape[0]) != nrows or int(out.shape[1]) != K:
+        raise ValueError("out must be [nrows, K, out_stride]")
+    if not 1 <= int(n) <= nrow <= min(row_stride, int(out.shape[2])):
+        raise ValueError("need 1 <= n <= nrow <= the strides")
+    jf = np.ascontiguousarray(jf, dtype=np.float64)
+    d_jf = torch.from_numpy(jf).to(trials.device)  # freed stream-ordered by torch's allocator
+    _C.jerk_resample_raw(trials.data_ptr(), row_stride, nrows, nrow, int(n), jf, d_jf.data_ptr(), out.data_ptr(),
+                         int(out.shape[2]), _s())
+    return out

@@ -2648,3 +2648,126 @@ def inject_filterbank(infile: str, outfile: Optional[str], signals, killmask=Non
         os.replace(tmp, outfile)
     return {"packed": packed, "values": values, "nclip": nclip, "touched": touched, "sigma": sigma, "unit": unit,
             "tables": tab, "truth": inject_truth(signals, tab, hdr, nsamps, unit, sigma)}
+
+
+# ------------------------------------------------------------------ jerk ----
+# The definition at the top of csrc/include/psoup/jerk.hpp in NumPy int64 /
+# float64: the oracle of csrc/kernels/jerk.hip and of the host steps.
+JERK_MAX_SPAN = 1 << 26
+JERK_MAX_TRIALS = 4096
+
+
+def jerk_factor(jerk: float, tsamp: float) -> float:
+    """jf of a jerk trial (m/s^3, float32) at the float32 tsamp."""
+    return ((float(np.float32(jerk)) * float(np.float32(tsamp))) * float(np.float32(tsamp))) / (6 * C_LIGHT)
+
+
+def jerk_shift(n: int, jf: float) -> np.ndarray:
+    """s(i), i < n: int64 rint (half to even) of three float64 products."""
+    i = np.arange(int(n), dtype=np.int64)
+    h = int(n) // 2
+    g = ((i.astype(np.float64) * (i - h).astype(np.float64)) * (i - int(n)).astype(np.float64)) * np.float64(jf)
+    return np.rint(g).astype(np.int64)
+
+
+def jerk_freq_factor(jerk: float, n: int, tsamp: float) -> float:
+    """1 + jerk T^2 / (12 c), T = n tsamp: apparent over true frequency."""
+    T = float(int(n)) * float(np.float32(tsamp))
+    return 1.0 + ((float(np.float32(jerk)) * T) * T) / (12.0 * C_LIGHT)
+
+
+def jerk_resample(x: np.ndarray, n: int, jf: float) -> np.ndarray:
+    """y of one row x [nrow] (any dtype) for the span n <= nrow."""
+    x = np.asarray(x)
+    n = int(n)
+    if not 1 <= n <= len(x):
+        raise ValueError("jerk_resample: the span must be in 1..nrow")
+    y = x.copy()
+    i = np.arange(n, dtype=np.int64)
+    y[:n] = x[np.clip(i + jerk_shift(n, jf), 0, n - 1)]
+    return y
+
+
+def jerk_check(n: int, jfs) -> None:
+    if int(n) > JERK_MAX_SPAN:
+        raise ValueError("jerk: series longer than 2^26 samples")
+    for f in jfs:
+        if not math.isfinite(f):
+            raise ValueError("jerk: a non-finite value (jerk factor)")
+        if (abs(f) * float(n)) * float(n) / 2.0 > 0.9:
+            raise ValueError("jerk: a trial moves more than 0.9 samples per sample at the ends")
+
+
+def jerk_width(dm: float, pulse_width: float, tsamp: float, cfreq: float, bw: float) -> float:
+    """AccelPlan::step's effective width at a DM, in seconds (float32 microseconds inside)."""
+    bw32, cf32, dm32 = float(np.float32(abs(bw))), float(np.float32(cfreq)), float(np.float32(dm))
+    tdm = np.float32(math.pow(8.3 * bw32 / math.pow(cf32, 3.0) * dm32, 2.0))
+    tpulse = np.float32(pulse_width) * np.float32(pulse_width)
+    ttsamp = np.float32(tsamp) * np.float32(tsamp)
+    w_us = np.sqrt(np.float32(np.float32(tdm + tpulse) + ttsamp))
+    return float(np.float32(w_us)) * 1.0e-6
+
+
+def jerk_plan(jerk_start: float, jerk_end: float, tol: float, step: float, pulse_width: float, n: int, tsamp: float,
+              cfreq: float, bw: float, dm: float) -> np.ndarray:
+    """The jerk trials (float32) of one DM: (float32)(k step) for every integer
+    k with jerk_start <= k step <= jerk_end; the one value when start == end."""
+    lo, hi = float(np.float32(jerk_start)), float(np.float32(jerk_end))
+    if not all(math.isfinite(float(v)) for v in (lo, hi, tol, step, pulse_width, tsamp, cfreq, bw)):
+        raise ValueError("jerk: a non-finite value (plan)")
+    if lo > hi:
+        raise ValueError("jerk: jerk_start > jerk_end")
+    if lo == hi:
+        return np.array([lo], dtype=np.float32)
+    if float(np.float32(step)) > 0:
+        st = float(np.float32(step))
+    else:
+        T = float(int(n)) * float(np.float32(tsamp))
+        t = float(np.float32(tol))
+        w = jerk_width(dm, pulse_width, tsamp, cfreq, bw)
+        st = ((2.0 * w) * math.sqrt(t * t - 1.0)) * ((72.0 * math.sqrt(3.0)) * C_LIGHT) / ((T * T) * T)
+    if not (math.isfinite(st) and st > 0):
+        raise ValueError("jerk: a non-finite value (the jerk step)")
+    ka, kb = math.ceil(lo / st), math.floor(hi / st)
+    if kb - ka + 1 > 2 * JERK_MAX_TRIALS:
+        raise ValueError("jerk: more than 4096 jerk trials per DM")
+    k0, k1 = int(ka), int(kb)
+    while float(k0) * st < lo:
+        k0 += 1
+    while float(k0 - 1) * st >= lo:
+        k0 -= 1
+    while float(k1) * st > hi:
+        k1 -= 1
+    while float(k1 + 1) * st <= hi:
+        k1 += 1
+    if k1 - k0 + 1 > JERK_MAX_TRIALS:
+        raise ValueError("jerk: more than 4096 jerk trials per DM")
+    if k1 < k0:
+        raise ValueError("jerk: no trial k * step in the range")
+    return np.array([float(k) * st for k in range(k0, k1 + 1)], dtype=np.float32)
+
+
+def jerk_distill(cands, tobs: float, span_s: float, tol: float, keep: bool = True):
+    """The jerk distillation of one DM: ``cands`` are (Cand, jerk) pairs; a
+    stable descending-S/N sort, then AccelerationDistiller's relation with the
+    edge f0 tol widened by f0 |jerk0 - jerk| T^2 / (12 c).  Returns the
+    surviving pairs; with ``keep`` the absorbed ones are appended to their
+    absorber's ``assoc``."""
+    c = sorted(cands, key=lambda p: -p[0].snr)
+    uniq = [True] * len(c)
+    toc = f32(tobs) / C_LIGHT
+    jw = (float(span_s) * float(span_s)) / (12.0 * C_LIGHT)
+    for idx in range(len(c)):
+        if not uniq[idx]:
+            continue
+        f0, a0, j0 = f32(c[idx][0].freq), f32(c[idx][0].acc), f32(c[idx][1])
+        for ii in range(idx + 1, len(c)):
+            f, a, j = f32(c[ii][0].freq), f32(c[ii][0].acc), f32(c[ii][1])
+            edge = f0 * f32(tol) + (f0 * abs(j0 - j)) * jw
+            af = f32(f0 + (a0 - a) * f0 * toc)
+            rel = (f0 - edge < f < af + edge) if af > f0 else (af - edge < f < f0 + edge)
+            if rel:
+                if keep:
+                    c[idx][0].assoc.append(c[ii][0])
+                uniq[ii] = False
+    return [p for p, u in zip(c, uniq) if u]

@@ -4,7 +4,8 @@ Used by the tests and benchmarks (there is no network access to real data).
 The generator produces quantised Gaussian noise plus a dispersed periodic
 pulse train whose arrival times follow the same dispersion law the pipeline
 searches for (delay_c = 4.15e3 * DM * (1/f_c^2 - 1/f_1^2) s), optionally with
-a constant line-of-sight acceleration (phase = (t - a t^2/(2c)) / P, a > 0 away).
+a constant line-of-sight acceleration (phase = (t - a t^2/(2c)) / P, a > 0 away)
+and a jerk (a further - j t^3/(6c), ``generate`` only).
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ class PulsarSpec:
     accel: float = 0.0          # m/s^2
     phase: float = 0.0
     alpha: float = 0.0          # spectral index about the band centre (filinject only)
+    jerk: float = 0.0           # m/s^3 (generate only): phase gains -jerk te^3/(6c)
 
 
 @dataclass
@@ -107,7 +109,10 @@ def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 
             te = t - delay[None, :]
             # +ve acceleration = away from the observer (distiller.hpp:164):
             # the apparent spin frequency drifts down
-            ph = (te - p.accel * te * te / (2 * C_LIGHT)) / p.period + p.phase
+            if p.jerk:  # the cubic term of a line-of-sight jerk (csrc/include/psoup/jerk.hpp)
+                ph = (te - p.accel * te * te / (2 * C_LIGHT) - p.jerk * te * te * te / (6 * C_LIGHT)) / p.period + p.phase
+            else:
+                ph = (te - p.accel * te * te / (2 * C_LIGHT)) / p.period + p.phase
             ph = ph - np.floor(ph)
             d = np.minimum(ph, 1.0 - ph)
             w = p.duty / 2.3548
