@@ -5,6 +5,7 @@
 #include "psoup/digi.hpp"
 #include "psoup/inject.hpp"
 #include "psoup/jerk.hpp"
+#include "psoup/orbit.hpp"
 #include "psoup/psrfits.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
@@ -805,6 +806,80 @@ bool parse_jerk_cmdline(JerkCmdLineOptions& j, const std::vector<std::string>& a
   if (exit_now && *exit_now) return true;
   if (a.max_num_threads != 1) {
     std::cerr << "Error: jerksearch runs on one device (-t 1); multi-GPU runs and checkpoints are not supported"
+              << std::endl;
+    return false;
+  }
+  if (a.npdmp < 0 || a.limit < 0) {
+    std::cerr << "Error: --npdmp and --limit must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_orbit_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_orbsearch.output", std::gmtime(&t));
+  return std::string(buf);
+}
+
+// a double that may be inf or nan: the refusal names it (make_orbit_setup), not the parser
+static Spec val_d(const char* l, const char* help, double& dst) {
+  return Spec{"", l, help, false, false,
+              [&dst](const std::string& v) {
+                char* end = nullptr;
+                dst = std::strtod(v.c_str(), &end);
+                return end != v.c_str() && *end == '\0';
+              },
+              nullptr};
+}
+
+bool parse_orbit_cmdline(OrbitCmdLineOptions& o, const std::vector<std::string>& argv, bool* exit_now) {
+  o.outfilename = default_orbit_output_filename();
+  CmdLineOptions& a = o.search;
+  a.max_num_threads = 1;
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", o.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_s("z", "zapfile", "Birdie list file", a.zapfilename),
+      val_n("t", "num_threads", "The number of GPUs to use: only 1 (one device; no multi-rank runs, no checkpoints)",
+            a.max_num_threads),
+      val_n("", "limit", "upper limit on number of candidates to write out", a.limit),
+      val_u("", "fft_size", "Transform size to use (defaults to lower power of two)", a.size),
+      val_n("", "dm_start", "First DM to dedisperse to", a.dm_start),
+      val_n("", "dm_end", "Last DM to dedisperse to", a.dm_end),
+      val_n("", "dm_tol", "DM smearing tolerance (1.11=10%)", a.dm_tol),
+      val_n("", "dm_pulse_width", "Minimum pulse width for which dm_tol is valid", a.dm_pulse_width),
+      val_n("", "acc_start", "First acceleration to resample to", a.acc_start),
+      val_n("", "acc_end", "Last acceleration to resample to", a.acc_end),
+      val_n("", "acc_tol", "Acceleration smearing tolerance (1.11=10%)", a.acc_tol),
+      val_n("", "acc_pulse_width", "Minimum pulse width for which acc_tol is valid", a.acc_pulse_width),
+      val_s("", "bankfile", "Template bank: lines `pb_s a1_ls phase` (# starts a comment)", o.bankfile),
+      val_d("pb_start", "Grid: first orbital period (s)", o.pb_start),
+      val_d("pb_end", "Grid: last orbital period (s)", o.pb_end),
+      val_n("", "npb", "Grid: orbital periods, geometric from pb_start to pb_end", o.npb),
+      val_d("a1_start", "Grid: first projected semi-major axis a sin i / c (light-seconds)", o.a1_start),
+      val_d("a1_end", "Grid: last projected semi-major axis (light-seconds)", o.a1_end),
+      val_n("", "na1", "Grid: semi-major axes, linear from a1_start to a1_end", o.na1),
+      val_n("", "nphase", "Grid: orbital phases, k / nphase turns", o.nphase),
+      val_n("n", "nharmonics", "Number of harmonic sums to perform", a.nharmonics),
+      val_n("", "npdmp", "Number of candidates to fold and pdmp", a.npdmp),
+      val_n("m", "min_snr", "The minimum S/N for a candidate", a.min_snr),
+      val_n("", "min_freq", "Lowest Fourier freqency to consider", a.min_freq),
+      val_n("", "max_freq", "Highest Fourier freqency to consider", a.max_freq),
+      val_s("", "accel_convention", "Acceleration-plan unit convention: legacy (default, golden) | reference",
+            a.accel_convention),
+      val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
+      sw("v", "verbose", "verbose mode", a.verbose),
+  };
+  if (!run_parser(specs, argv,
+                  "Peasoup orbsearch extension - circular-orbit templates around the acceleration search (one device)",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.max_num_threads != 1) {
+    std::cerr << "Error: orbsearch runs on one device (-t 1); multi-GPU runs and checkpoints are not supported"
               << std::endl;
     return false;
   }

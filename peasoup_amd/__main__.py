@@ -10,7 +10,8 @@ scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``py
 [fildigi flags]`` for the 8-bit digitisation of a 16 / 32-bit or ascending-band filterbank, ``python -m peasoup_amd
 fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file, ``python -m peasoup_amd inject
 [filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank, ``python -m peasoup_amd jerk
-[jerksearch flags]`` for the acceleration search repeated over jerk trials) -- the peasoup CLI as a
+[jerksearch flags]`` for the acceleration search repeated over jerk trials, ``python -m peasoup_amd orb
+[orbsearch flags]`` for the one repeated over circular-orbit templates) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -96,6 +97,8 @@ def main(argv=None) -> int:
         return _main_inject(["filinject"] + argv[2:])
     if len(argv) > 1 and argv[1] == "jerk":
         return _main_jerk(["jerksearch"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "orb":
+        return _main_orbit(["orbsearch"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -363,6 +366,26 @@ def _main_jerk(argv) -> int:
         _fail_hard("jerk", e)
     if res is not None and args.search.verbose:
         print(f"jerksearch: {len(res.candidates)} candidates from {res.jerk_trials} DM-jerk trials "
+              f"({res.accel_trials} acceleration trials) to {args.outfilename}")
+    return 0
+
+
+def _main_orbit(argv) -> int:
+    from . import _C
+    from .models.orbit import run_orbit_search
+
+    ok, exit_now, args = _C.parse_orbit_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = run_orbit_search(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("orb", e)
+    if res is not None and args.search.verbose:
+        print(f"orbsearch: {len(res.candidates)} candidates from {res.template_trials} DM-template trials "
               f"({res.accel_trials} acceleration trials) to {args.outfilename}")
     return 0
 

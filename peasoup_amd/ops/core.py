@@ -1154,3 +1154,53 @@ def jerk_resample(trials: torch.Tensor, n: int, jerks: Sequence[float], tsamp: f
     _C.jerk_resample_raw(trials.data_ptr(), row_stride, nrows, nrow, int(n), jf, d_jf.data_ptr(), out.data_ptr(),
                          int(out.shape[2]), _s())
     return out
+
+
+# ----------------------------------------------------------------- orbit ----
+_ORBIT_TABLES: Dict = {}
+
+
+def orbit_quantise(templates, tsamp: float):
+    """The definition's (W, F, Aq) of circular-orbit templates (pb s, a1
+    light-seconds, phase turns) at the float32 ``tsamp``; every refusal of the
+    quantisation is raised by name.  Equals ``utils.reference.orbit_quantise``."""
+    ts = float(np.float32(tsamp))
+    return [tuple(int(v) for v in _C.orbit_quantise(float(pb), float(a1), float(ph), ts)) for pb, a1, ph in templates]
+
+
+def _orbit_table(device: torch.device) -> torch.Tensor:
+    key = (device.type, device.index)
+    if key not in _ORBIT_TABLES:
+        _ORBIT_TABLES[key] = torch.from_numpy(np.ascontiguousarray(_C.orbit_sine_table(), dtype=np.int32)).to(device)
+    return _ORBIT_TABLES[key]
+
+
+def orbit_resample(trials: torch.Tensor, n: int, templates, tsamp: float, nrow: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None, quant=None) -> torch.Tensor:
+    """The orbit_resample kernel: uint8 rows ``trials`` [nrows, row_stride], of
+    which the first ``nrow`` samples (default: all) are the row and the first
+    ``n`` the resampled span, re-indexed at each template.  Returns ``out``
+    [nrows, K, out_stride] (allocated as [nrows, K, nrow] when not given) with
+    out[r, k, :nrow] the definition's y; bytes past nrow are not written.
+    ``quant`` gives the quantised templates (W, F, Aq) themselves instead of
+    ``templates`` and ``tsamp``.  Equals ``utils.reference.orbit_resample`` byte
+    for byte."""
+    _check(trials, torch.uint8, "trials")
+    if trials.dim() != 2:
+        raise ValueError("trials must be [nrows, row_stride]")
+    nrows, row_stride = int(trials.shape[0]), int(trials.shape[1])
+    nrow = row_stride if nrow is None else int(nrow)
+    q = orbit_quantise(templates, tsamp) if quant is None else [tuple(int(v) for v in t) for t in quant]
+    K = len(q)
+    if out is None:
+        out = torch.empty((nrows, K, nrow), dtype=torch.uint8, device=trials.device)
+    _check(out, torch.uint8, "out")
+    if out.dim() != 3 or int(out.shape[0]) != nrows or int(out.shape[1]) != K:
+        raise ValueError("out must be [nrows, K, out_stride]")
+    if not 1 <= int(n) <= nrow <= min(row_stride, int(out.shape[2])):
+        raise ValueError("need 1 <= n <= nrow <= the strides")
+    packed = np.array([[t[0], t[1], t[2] & 0xFFFFFFFFFFFFFFFF] for t in q], dtype=np.uint64).reshape(-1, 3)
+    d_q = torch.from_numpy(packed.view(np.int64)).to(trials.device)  # freed stream-ordered by torch's allocator
+    _C.orbit_resample_raw(trials.data_ptr(), row_stride, nrows, nrow, int(n), q, d_q.data_ptr(),
+                          _orbit_table(trials.device).data_ptr(), out.data_ptr(), int(out.shape[2]), _s())
+    return out

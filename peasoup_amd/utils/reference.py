@@ -2771,3 +2771,158 @@ def jerk_distill(cands, tobs: float, span_s: float, tol: float, keep: bool = Tru
                     c[idx][0].assoc.append(c[ii][0])
                 uniq[ii] = False
     return [p for p, u in zip(c, uniq) if u]
+
+
+# ----------------------------------------------------------------- orbit ----
+# The definition at the top of csrc/include/psoup/orbit.hpp in NumPy uint64 /
+# int64: the oracle of csrc/kernels/orbit.hip and of the host steps.  The sine
+# table is built with math.sin, the C library's double sine that the native
+# table is built with.
+ORBIT_MAX_SPAN = 1 << 26
+ORBIT_MAX_TEMPLATES = 1 << 20
+_ORBIT_TABLE = None
+
+
+def orbit_sine_table() -> np.ndarray:
+    """int32 T[0..4096]: a turn in 4096 steps, Q30, built from the first quadrant."""
+    global _ORBIT_TABLE
+    if _ORBIT_TABLE is None:
+        t = np.zeros(4097, dtype=np.int64)
+        for j in range(1025):
+            t[j] = int(np.rint(math.ldexp(math.sin(float(j) * (math.pi / 2048)), 30)))
+        for j in range(1025):
+            t[2048 - j] = t[j]
+        for j in range(2049):
+            t[2048 + j] = -t[j]
+        _ORBIT_TABLE = t.astype(np.int32)
+        _ORBIT_TABLE.setflags(write=False)
+    return _ORBIT_TABLE
+
+
+def orbit_quantise(pb: float, a1: float, ph: float, tsamp: float) -> Tuple[int, int, int]:
+    """(W, F, Aq) of a template at the float32 tsamp; raises ValueError by name."""
+    pb, a1, ph, ts = float(pb), float(a1), float(ph), float(np.float32(tsamp))
+    if not all(math.isfinite(v) for v in (pb, a1, ph, ts)):
+        raise ValueError("orbit: a non-finite value")
+    if pb < 64.0 * ts:
+        raise ValueError("orbit: pb < 64 tsamp")
+    if a1 < 0.0:
+        raise ValueError("orbit: a1 < 0")
+    W = int(np.rint(math.ldexp(ts / pb, 64)))
+    r = ph - math.floor(ph)
+    if r >= 1.0:
+        r = 0.0
+    F = int(math.ldexp(r, 64))
+    aq = float(np.rint((a1 / ts) * 256.0))
+    if aq >= 2.0 ** 30:
+        raise ValueError("orbit: Aq >= 2^30")
+    return W, F, int(aq)
+
+
+def orbit_sine(th: np.ndarray) -> np.ndarray:
+    """S(th) of uint64 phases, int64."""
+    T = orbit_sine_table().astype(np.int64)
+    th = np.asarray(th, dtype=np.uint64)
+    j = (th >> np.uint64(52)).astype(np.int64)
+    f = ((th >> np.uint64(32)) & np.uint64(0xFFFFF)).astype(np.int64)
+    return T[j] + (((T[j + 1] - T[j]) * f + (1 << 19)) >> 20)
+
+
+def orbit_shift(n: int, q: Tuple[int, int, int]) -> np.ndarray:
+    """s(i), i < n, int64: wrapping uint64 phases, int64 arithmetic shifts."""
+    W, F, Aq = (int(v) for v in q)
+    with np.errstate(over="ignore"):
+        th = np.uint64(F) + np.arange(int(n), dtype=np.uint64) * np.uint64(W)
+    sf = int(orbit_sine(np.array([F], dtype=np.uint64))[0])
+    return (np.int64(Aq) * (orbit_sine(th) - sf) + (1 << 37)) >> 38
+
+
+def orbit_resample(x: np.ndarray, n: int, q: Tuple[int, int, int]) -> np.ndarray:
+    """y of one row x [nrow] (any dtype) for the span n <= nrow."""
+    x = np.asarray(x)
+    n = int(n)
+    if not 1 <= n <= len(x):
+        raise ValueError("orbit_resample: the span must be in 1..nrow")
+    y = x.copy()
+    i = np.arange(n, dtype=np.int64)
+    y[:n] = x[np.clip(i + orbit_shift(n, q), 0, n - 1)]
+    return y
+
+
+def orbit_beta(pb: float, a1: float) -> float:
+    return ((2.0 * math.pi) * float(a1)) / float(pb)
+
+
+def orbit_check(n: int, bank, tsamp: float) -> None:
+    if int(n) > ORBIT_MAX_SPAN:
+        raise ValueError("orbit: series longer than 2^26 samples")
+    if len(bank) == 0:
+        raise ValueError("orbit: an empty bank")
+    if len(bank) > ORBIT_MAX_TEMPLATES:
+        raise ValueError("orbit: more than 2^20 templates")
+    for pb, a1, ph in bank:
+        orbit_quantise(pb, a1, ph, tsamp)
+        if orbit_beta(pb, a1) > 0.9:
+            raise ValueError("orbit: a template moves more than 0.9 samples per sample")
+
+
+def orbit_parse_bank(text: str) -> List[Tuple[float, float, float]]:
+    """The (pb, a1, ph) of a bank file's text: `#` starts a comment, columns past the third are ignored."""
+    bank = []
+    for ln, line in enumerate(text.split("\n"), 1):
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        try:
+            if len(tok) < 3:
+                raise ValueError
+            bank.append(tuple(float(v) for v in tok[:3]))
+        except ValueError:
+            raise ValueError(f"orbit: bank line {ln} is malformed") from None
+    return bank
+
+
+def orbit_grid(pb_start: float, pb_end: float, npb: int, a1_start: float, a1_end: float, na1: int,
+               nphase: int) -> List[Tuple[float, float, float]]:
+    """The regular grid: pb geometric, a1 linear, phase k / nphase; pb slowest, phase fastest."""
+    if min(npb, na1, nphase) < 1:
+        raise ValueError("orbit: --npb, --na1 and --nphase must be at least 1")
+    if npb * na1 * nphase > ORBIT_MAX_TEMPLATES:
+        raise ValueError("orbit: more than 2^20 templates")
+    bank = []
+    for p in range(npb):
+        pb = float(pb_start)
+        if p > 0:
+            pb = float(pb_end) if p == npb - 1 else \
+                float(pb_start) * math.pow(float(pb_end) / float(pb_start), float(p) / float(npb - 1))
+        for a in range(na1):
+            a1 = float(a1_start)
+            if a > 0:
+                a1 = float(a1_end) if a == na1 - 1 else \
+                    float(a1_start) + (float(a1_end) - float(a1_start)) * (float(a) / float(na1 - 1))
+            for f in range(nphase):
+                bank.append((pb, a1, float(f) / float(nphase)))
+    return bank
+
+
+def orbit_distill(cands, beta, tol: float, keep: bool = True):
+    """The orbit distillation of one DM: ``cands`` are (Cand, template index)
+    pairs, ``beta`` the templates' 2 pi a1 / pb.  A stable descending-S/N sort;
+    a survivor absorbs a weaker candidate of another template when
+    |f / f0 - 1| <= tol + beta0 + beta.  The plain scan, survivors times all
+    candidates.  Returns the surviving pairs; with ``keep`` the absorbed ones
+    are appended to their absorber's ``assoc``."""
+    c = sorted(cands, key=lambda p: -p[0].snr)
+    uniq = [True] * len(c)
+    for idx in range(len(c)):
+        if not uniq[idx]:
+            continue
+        f0, b0 = f32(c[idx][0].freq), float(beta[c[idx][1]])
+        for ii in range(idx + 1, len(c)):
+            if c[ii][1] == c[idx][1]:
+                continue
+            if abs(f32(c[ii][0].freq) / f0 - 1.0) <= (f32(tol) + b0) + float(beta[c[ii][1]]):
+                if keep:
+                    c[idx][0].assoc.append(c[ii][0])
+                uniq[ii] = False
+    return [p for p, u in zip(c, uniq) if u]

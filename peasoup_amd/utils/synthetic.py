@@ -5,7 +5,8 @@ The generator produces quantised Gaussian noise plus a dispersed periodic
 pulse train whose arrival times follow the same dispersion law the pipeline
 searches for (delay_c = 4.15e3 * DM * (1/f_c^2 - 1/f_1^2) s), optionally with
 a constant line-of-sight acceleration (phase = (t - a t^2/(2c)) / P, a > 0 away)
-and a jerk (a further - j t^3/(6c), ``generate`` only).
+and a jerk (a further - j t^3/(6c), ``generate`` only), or on a circular orbit
+(``generate`` only).
 """
 from __future__ import annotations
 
@@ -28,6 +29,9 @@ class PulsarSpec:
     accel: float = 0.0          # m/s^2
     phase: float = 0.0
     alpha: float = 0.0          # spectral index about the band centre (filinject only)
+    # (pb s, a1 light-seconds, phase turns) of a circular orbit or None (generate only): a pulse emitted at tau
+    # arrives at tau + a1 [sin 2 pi (tau / pb + ph) - sin 2 pi ph] (csrc/include/psoup/orbit.hpp)
+    orbit: Optional[Tuple[float, float, float]] = None
     jerk: float = 0.0           # m/s^3 (generate only): phase gains -jerk te^3/(6c)
 
 
@@ -107,6 +111,11 @@ def generate(nsamps: int, header: Dict, pulsars=(), seed: int = 0, chunk: int = 
         for p in pulsars:
             delay = 4.15e3 * p.dm * (1.0 / freqs ** 2 - 1.0 / fch1 ** 2)  # seconds
             te = t - delay[None, :]
+            if p.orbit is not None:  # the orbit-frame time tau of te = tau + D(tau), by fixed-point iteration
+                pb, a1, oph = (float(v) for v in p.orbit)
+                t_arr, te = te, te
+                for _ in range(8):
+                    te = t_arr - a1 * (np.sin(2 * np.pi * (te / pb + oph)) - np.sin(2 * np.pi * oph))
             # +ve acceleration = away from the observer (distiller.hpp:164):
             # the apparent spin frequency drifts down
             if p.jerk:  # the cubic term of a line-of-sight jerk (csrc/include/psoup/jerk.hpp)
