@@ -1435,13 +1435,6 @@ struct HarmTileG {
     return off;
   }
   static constexpr int TOTAL = offset(NREG);
-  static constexpr int iters() {
-    int n = 0;
-    for (int h = 0; h <= NLEV; ++h)
-      for (int m = 1; m < mend(h); m += 2) n += (chunks(h, m) + 255) / 256;
-    return n;
-  }
-  static constexpr int ITERS = iters();
   static constexpr int GW = B / 32;              // groups per wave (4 waves, 8 bins per group)
   static constexpr int GP = (GW + 63) / 64;      // groups per lane
 };
@@ -1500,51 +1493,53 @@ harmonic_peaks_q8g_kernel(const float* __restrict__ P, uint64_t pstride, const u
   // ---- staging: the raw bytes as in harmonic_peaks_q8_kernel (the
   // fundamentals as one more range), and each chunk's two block maxima
   const bool interior = b0 + B <= hi;
-  uint4 tmp[Tl::ITERS];
-  if (interior) {
-    const uint32_t vo = 16u * static_cast<uint32_t>(t);
-    int it = 0;
+  // The ranges lie back to back in LDS, so chunk c of the tile -- all ranges
+  // counted through -- goes to lds[16 c] and its maxima to cmx[2 c].  Thread t
+  // takes chunks t, t + 256, ...: every wave stages and reduces at most
+  // ceil(NCH / 256) chunks per lane.  (Dealt range by range the four waves
+  // took 8 / 7 / 5 / 3 at 3 levels and the barrier waited for the 8: 1.89 us
+  // per trial against 1.63, profiles/r7_harm_maxima/.)  Only the chunk's
+  // source needs its range: r0s(h, m) + 16 (c - first), a per-lane select
+  // over the (at most three) ranges a round of 256 chunks meets.
+  constexpr int NCH = Tl::TOTAL / 16, NIT = (NCH + 255) / 256;
+  uint4 tmp[NIT];
+  int srcs[NIT];  // each chunk's first byte in the row (shifted coordinate, a multiple of 16, >= 0)
+#pragma unroll
+  for (int j = 0; j < NIT; ++j) {
+    const int c = t + 256 * j;
+    int src = 0;
 #pragma unroll
     for (int h = 0; h <= NLEV; ++h) {
 #pragma unroll
       for (int m = 1; m < Tl::mend(h); m += 2) {
-        const int r0 = r0s(h, m);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(q - qs + r0), 0, static_cast<int>(qstride) - r0, 0x00020000);
-#pragma unroll
-        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
-          if (t + 256 * e < Tl::chunks(h, m))
-            tmp[it] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 4096u * e, 0, 0));
+        const int first = Tl::offset(Tl::region(h, m)) / 16;
+        if (first < 256 * j + 256 && first + Tl::chunks(h, m) > 256 * j) {
+          const int a = r0s(h, m) - 16 * first;  // block-uniform
+          src = c >= first ? a : src;            // ranges in LDS order: the last one at or below c
+        }
       }
     }
-  } else {
-    int it = 0;
-#pragma unroll
-    for (int h = 0; h <= NLEV; ++h) {
-#pragma unroll
-      for (int m = 1; m < Tl::mend(h); m += 2) {
-        const int r0 = r0s(h, m) - qs;
-#pragma unroll
-        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
-          tmp[it] = load_q16(q, r0 + 16 * (t + 256 * e), last);
-      }
-    }
+    srcs[j] = src + 16 * c;
   }
-  {
-    int it = 0;
+  if (interior) {
+    // (reads past the row's qstride bytes return 0: chunks beyond the spectrum, never used)
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(q - qs), 0, static_cast<int>(qstride), 0x00020000);
 #pragma unroll
-    for (int h = 0; h <= NLEV; ++h) {
+    for (int j = 0; j < NIT; ++j)
+      if (t + 256 * j < NCH)
+        tmp[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, srcs[j], 0, 0));
+  } else {
 #pragma unroll
-      for (int m = 1; m < Tl::mend(h); m += 2) {
-        uint4* dst = reinterpret_cast<uint4*>(lds + Tl::offset(Tl::region(h, m)));
-        uint16_t* dmx = reinterpret_cast<uint16_t*>(cmx + Tl::offset(Tl::region(h, m)) / 8);
+    for (int j = 0; j < NIT; ++j)
+      if (t + 256 * j < NCH) tmp[j] = load_q16(q, srcs[j] - qs, last);
+  }
 #pragma unroll
-        for (int e = 0; e < (Tl::chunks(h, m) + 255) / 256; ++e, ++it)
-          if (t + 256 * e < Tl::chunks(h, m)) {
-            dst[t + 256 * e] = tmp[it];
-            dmx[t + 256 * e] = static_cast<uint16_t>(block_max2(tmp[it]));
-          }
-      }
+  for (int j = 0; j < NIT; ++j) {
+    const int c = t + 256 * j;
+    if (c < NCH) {
+      reinterpret_cast<uint4*>(lds)[c] = tmp[j];
+      reinterpret_cast<uint16_t*>(cmx)[c] = static_cast<uint16_t>(block_max2(tmp[j]));
     }
   }
   __syncthreads();
