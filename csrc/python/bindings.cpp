@@ -131,6 +131,7 @@ void bind_inject(py::module_& m);   // bind_inject.cpp
 void bind_bopt(py::module_& m);     // bind_bopt.cpp
 void bind_jerk(py::module_& m);     // bind_jerk.cpp
 void bind_orbit(py::module_& m);    // bind_orbit.cpp
+void bind_sideband(py::module_& m); // bind_sideband.cpp
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "peasoup_amd native core (C++/HIP for gfx950)";
@@ -713,6 +714,7 @@ PYBIND11_MODULE(_C, m) {
   bind_bopt(m);
   bind_jerk(m);
   bind_orbit(m);
+  bind_sideband(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");
   k.def("unpack_transpose", [](uintptr_t packed, uint64_t nsamps, int nchans, int nbits, uintptr_t out,

@@ -6,6 +6,7 @@
 #include "psoup/inject.hpp"
 #include "psoup/jerk.hpp"
 #include "psoup/orbit.hpp"
+#include "psoup/sideband.hpp"
 #include "psoup/psrfits.hpp"
 #include "psoup/foldcube.hpp"
 #include "psoup/rfi.hpp"
@@ -885,6 +886,57 @@ bool parse_orbit_cmdline(OrbitCmdLineOptions& o, const std::vector<std::string>&
   }
   if (a.npdmp < 0 || a.limit < 0) {
     std::cerr << "Error: --npdmp and --limit must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_sb_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_sbsearch.output", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_sb_cmdline(SbCmdLineOptions& o, const std::vector<std::string>& argv, bool* exit_now) {
+  o.outfilename = default_sb_output_filename();
+  CmdLineOptions& a = o.search;
+  a.max_num_threads = 1;
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("o", "outfilename", "The output filename", o.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_s("z", "zapfile", "Birdie list file", a.zapfilename),
+      val_n("t", "num_threads", "The number of GPUs to use: only 1 (one device; no multi-rank runs, no checkpoints)",
+            a.max_num_threads),
+      val_n("", "limit", "upper limit on number of candidates to write out", a.limit),
+      val_u("", "fft_size", "Transform size to use (defaults to lower power of two)", a.size),
+      val_n("", "dm_start", "First DM to dedisperse to", a.dm_start),
+      val_n("", "dm_end", "Last DM to dedisperse to", a.dm_end),
+      val_n("", "dm_tol", "DM smearing tolerance (1.11=10%)", a.dm_tol),
+      val_n("", "dm_pulse_width", "Minimum pulse width for which dm_tol is valid", a.dm_pulse_width),
+      val_f("min_freq", "Lowest Fourier freqency to consider", a.min_freq),
+      val_f("max_freq", "Highest Fourier freqency to consider", a.max_freq),
+      val_f("min_power", "The minimum secondary power S for an event", o.min_power),
+      val_n("", "m_min", "Smallest segment size, M = 2^m_min bins (5..13)", o.m_min),
+      val_n("", "m_max", "Largest segment size, M = 2^m_max bins (5..13)", o.m_max),
+      val_n("", "j_min", "Lowest bin of the secondary spectrum searched", o.j_min),
+      val_f("clip", "Powers above this many band means are lowered to it", o.clip),
+      val_s("", "dedisp_kernel", "Dedispersion kernel: auto | mfma | valu | direct | packed2", a.dedisp_kernel),
+      sw("v", "verbose", "verbose mode", a.verbose),
+  };
+  if (!run_parser(specs, argv,
+                  "Peasoup sbsearch extension - sideband (phase-modulation) search for short orbits (one device)",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.max_num_threads != 1) {
+    std::cerr << "Error: sbsearch runs on one device (-t 1); multi-GPU runs and checkpoints are not supported"
+              << std::endl;
+    return false;
+  }
+  if (a.limit < 0) {
+    std::cerr << "Error: --limit must be non-negative" << std::endl;
     return false;
   }
   return true;

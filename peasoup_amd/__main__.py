@@ -11,7 +11,8 @@ scrunch [filscrunch flags]`` for the subbanded / time-scrunched filterbank, ``py
 fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file, ``python -m peasoup_amd inject
 [filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank, ``python -m peasoup_amd jerk
 [jerksearch flags]`` for the acceleration search repeated over jerk trials, ``python -m peasoup_amd orb
-[orbsearch flags]`` for the one repeated over circular-orbit templates) -- the peasoup CLI as a
+[orbsearch flags]`` for the one repeated over circular-orbit templates, ``python -m peasoup_amd sb
+[sbsearch flags]`` for the sideband search for short orbits) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -99,6 +100,8 @@ def main(argv=None) -> int:
         return _main_jerk(["jerksearch"] + argv[2:])
     if len(argv) > 1 and argv[1] == "orb":
         return _main_orbit(["orbsearch"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "sb":
+        return _main_sb(["sbsearch"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -387,6 +390,26 @@ def _main_orbit(argv) -> int:
     if res is not None and args.search.verbose:
         print(f"orbsearch: {len(res.candidates)} candidates from {res.template_trials} DM-template trials "
               f"({res.accel_trials} acceleration trials) to {args.outfilename}")
+    return 0
+
+
+def _main_sb(argv) -> int:
+    from . import _C
+    from .models.sideband import run_sideband_search
+
+    ok, exit_now, args = _C.parse_sb_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = run_sideband_search(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("sb", e)
+    if res is not None and args.search.verbose:
+        print(f"sbsearch: {len(res.candidates)} candidates from {res.events} events of "
+              f"{len(res.setup.dm_list)} DM trials to {args.outfilename}")
     return 0
 
 

@@ -1204,3 +1204,109 @@ def orbit_resample(trials: torch.Tensor, n: int, templates, tsamp: float, nrow: 
     _C.orbit_resample_raw(trials.data_ptr(), row_stride, nrows, nrow, int(n), q, d_q.data_ptr(),
                           _orbit_table(trials.device).data_ptr(), out.data_ptr(), int(out.shape[2]), _s())
     return out
+
+
+# -------------------------------------------------------------- sideband ----
+_SB_TWIDDLES: Dict = {}
+SB_EVENT_DTYPE = [("dm_idx", "<i4"), ("m", "<i4"), ("seg", "<i4"), ("j", "<i4"), ("S", "<f4")]  # SbEvent
+
+
+def _sb_twiddles(device: torch.device) -> torch.Tensor:
+    key = (device.type, device.index)
+    if key not in _SB_TWIDDLES:
+        _SB_TWIDDLES[key] = torch.from_numpy(np.ascontiguousarray(_C.sb_twiddles(), dtype=np.complex64)).to(device)
+    return _SB_TWIDDLES[key]
+
+
+def _sb_zap_words(zapmask, nbins: int, device) -> Tuple[Optional[torch.Tensor], int]:
+    """A boolean mask per bin (True = zapped) -> (build_zap_mask's uint32 words
+    on the device as int32, or None; the host copy's bits as a bool array)."""
+    if zapmask is None:
+        return None, None
+    z = np.zeros((nbins + 31) // 32 * 32, dtype=bool)
+    z[:nbins] = np.asarray(zapmask, dtype=bool)[:nbins]
+    words = np.packbits(z.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+    return torch.from_numpy(words.view(np.int32).copy()).to(device), z[:nbins]
+
+
+def sideband_power(spec: torch.Tensor, k_lo: int, k_hi: int, zapmask=None, out: Optional[torch.Tensor] = None):
+    """The sb_power kernels: complex64 spectra ``spec`` [nrows, nbins] ->
+    (mu float64 [nrows], P float32 [nrows, stride]) with P written on [k_lo,
+    k_hi) only (``out`` given: into it; else a zeroed [nrows, nbins rounded up
+    to 4]).  ``zapmask``: a boolean per bin (True = zapped) or None.  Equals
+    ``utils.reference.sideband_power`` (mu to 1e-12, P to 4 ulp)."""
+    _check(spec, torch.complex64, "spec")
+    if spec.dim() != 2:
+        raise ValueError("spec must be [nrows, nbins]")
+    nrows, nb = int(spec.shape[0]), int(spec.shape[1])
+    k_lo, k_hi = int(k_lo), int(k_hi)
+    if not 0 <= k_lo < k_hi <= nb:
+        raise ValueError("need 0 <= k_lo < k_hi <= nbins")
+    dev = spec.device
+    if out is None:
+        out = torch.zeros((nrows, (nb + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    _check(out, torch.float32, "out")
+    if out.dim() != 2 or int(out.shape[0]) != nrows or int(out.shape[1]) < k_hi:
+        raise ValueError("out must be [nrows, stride >= k_hi]")
+    words, bits = _sb_zap_words(zapmask, nb, dev)
+    count = (k_hi - k_lo) if bits is None else int((k_hi - k_lo) - np.count_nonzero(bits[k_lo:k_hi]))
+    if count < 1:
+        raise ValueError("sideband: the band has no unzapped bin")
+    nranges = (k_hi - k_lo + _C.SB_RANGE - 1) // _C.SB_RANGE
+    partials = torch.empty((nrows, nranges), dtype=torch.float64, device=dev)
+    mu = torch.empty(nrows, dtype=torch.float64, device=dev)
+    _C.sb_power_raw(spec.data_ptr(), nb, nrows, 0 if words is None else words.data_ptr(), k_lo, k_hi, count,
+                    partials.data_ptr(), mu.data_ptr(), out.data_ptr(), int(out.shape[1]), _s())
+    return mu, out
+
+
+def sideband_search(P: torch.Tensor, k_lo: int, k_hi: int, m_lo: int = 5, m_hi: int = 13, j_min: int = 2,
+                    clip: float = 32.0, min_power: float = 30.0, dm0: int = 0, capacity: int = 65536,
+                    dense: bool = True):
+    """The sb_search kernel on float32 rows ``P`` [nrows, stride] (stride a
+    multiple of 4; read on [k_lo, k_hi) only).  Returns a dict: ``best_S``
+    float32 and ``best_j`` int32 [nrows, m_hi - m_lo + 1, seg_stride] (``dense``;
+    entries past a size's segment count keep the poison, a NaN as float32),
+    ``nseg`` per size, ``count`` (all events of S >= min_power, which may pass
+    ``capacity``) and ``events``, the min(count, capacity) records written, a
+    structured array (SB_EVENT_DTYPE).  Every output lies between poisoned
+    guards; a changed guard raises.  Equals ``utils.reference.sideband_search``
+    within its bound."""
+    _check(P, torch.float32, "P")
+    if P.dim() != 2:
+        raise ValueError("P must be [nrows, stride]")
+    nrows, stride = int(P.shape[0]), int(P.shape[1])
+    g = _C.sb_band_geometry(int(k_lo), int(k_hi), int(m_lo), int(m_hi))
+    if int(k_hi) > stride:
+        raise ValueError("the band passes a row")
+    dev = P.device
+    nm = int(m_hi) - int(m_lo) + 1
+    ss = max(int(g.seg_stride), 1)
+    capacity = int(capacity)
+    ev_words = _C.SB_EVENT_BYTES // 4
+    bs = _guarded(nrows, (nm, ss), dev) if dense else None
+    bj = _guarded(nrows, (nm, ss), dev) if dense else None
+    ev = _guarded(max(capacity, 1), (ev_words,), dev)
+    cnt = _guarded(1, (1,), dev)
+    cnt[1] = 0
+    _C.sb_search_raw(P.data_ptr(), stride, nrows, int(k_lo), int(k_hi), int(m_lo), int(m_hi), int(j_min), float(clip),
+                     float(min_power), int(dm0), _sb_twiddles(dev).data_ptr(),
+                     bs[1:].data_ptr() if dense else 0, bj[1:].data_ptr() if dense else 0, ss,
+                     ev[1:].data_ptr(), capacity, cnt[1:].data_ptr(), _s())
+    torch.cuda.current_stream().synchronize()
+    for buf, name in ((bs, "best_S"), (bj, "best_j"), (ev, "events"), (cnt, "count")):
+        if buf is not None:
+            _check_guards(buf, "sideband_search " + name)
+    count = int(cnt[1, 0])
+    nwritten = min(count, capacity)
+    rows = ev[1:1 + max(capacity, 1)].cpu().numpy()
+    if capacity == 0 and not bool((ev[1] == _POISON).all()):
+        raise RuntimeError("sideband_search events: written at a capacity of 0")
+    if not bool((ev[1 + nwritten:1 + max(capacity, 1)] == _POISON).all()) and capacity > 0:
+        raise RuntimeError("sideband_search events: a slot past the count was written")
+    events = np.ascontiguousarray(rows[:nwritten]).view(SB_EVENT_DTYPE).reshape(-1)
+    res = {"count": count, "events": events, "nseg": [int(n) for n in g.nseg], "seg_stride": ss}
+    if dense:
+        res["best_S"] = bs[1:-1].view(torch.float32)
+        res["best_j"] = bj[1:-1]
+    return res

@@ -2926,3 +2926,139 @@ def orbit_distill(cands, beta, tol: float, keep: bool = True):
                     c[idx][0].assoc.append(c[ii][0])
                 uniq[ii] = False
     return [p for p, u in zip(c, uniq) if u]
+
+
+# ------------------------------------------------------------- sideband ----
+# The sideband (phase-modulation) search of csrc/include/psoup/sideband.hpp in
+# float64 NumPy.  An extension beyond the reference.
+SB_RANGE = 4096
+SB_RANGE_LANES = 256
+
+
+def sideband_geometry(min_freq: float, max_freq: float, fft_size: int, tsamp: float, m_lo: int = 5, m_hi: int = 13) -> Dict:
+    """The definition's T, k_lo, k_hi and segments per size (float32 inputs)."""
+    T = float(fft_size) * float(np.float32(tsamp))
+    top = fft_size // 2
+    k_lo = int(min(max(math.ceil(float(np.float32(min_freq)) * T), 0), top))
+    k_hi = int(min(max(math.floor(float(np.float32(max_freq)) * T), 0), top))
+    k_hi = max(k_hi, k_lo)
+    return {"tobs": T, "k_lo": k_lo, "k_hi": k_hi,
+            "nseg": {m: sideband_nseg(k_hi - k_lo, m) for m in range(m_lo, m_hi + 1)}}
+
+
+def sideband_nseg(band: int, m: int) -> int:
+    M = 1 << m
+    return 0 if band < M else (band - M) // (M // 2) + 1
+
+
+def sideband_power(spec: np.ndarray, k_lo: int, k_hi: int, zapmask=None) -> Tuple[float, np.ndarray]:
+    """Step 2 on one complex64 spectrum: (mu, P float32 [len(spec)], zero outside
+    the band).  zapmask: a boolean array per bin (True = zapped) or None.  mu is
+    summed in the definition's order."""
+    spec = np.asarray(spec)
+    re = spec.real.astype(np.float64)
+    im = spec.imag.astype(np.float64)
+    p = re * re + im * im
+    zap = np.zeros(len(p), dtype=bool) if zapmask is None else np.asarray(zapmask, dtype=bool)
+    band = k_hi - k_lo
+    nranges = (band + SB_RANGE - 1) // SB_RANGE
+    v = np.zeros(nranges * SB_RANGE)
+    v[:band] = np.where(zap[k_lo:k_hi], 0.0, p[k_lo:k_hi])
+    v = v.reshape(nranges, SB_RANGE // SB_RANGE_LANES, SB_RANGE_LANES)
+    a = np.zeros((nranges, SB_RANGE_LANES))
+    for u in range(SB_RANGE // SB_RANGE_LANES):
+        a = a + v[:, u, :]
+    s = SB_RANGE_LANES // 2
+    while s >= 1:
+        a = a[:, :s] + a[:, s:2 * s]
+        s //= 2
+    total = 0.0
+    for r in range(nranges):
+        total = total + float(a[r, 0])
+    count = int(band - np.count_nonzero(zap[k_lo:k_hi]))
+    if count < 1:
+        raise ValueError("sideband: the band has no unzapped bin")
+    mu = total / count
+    P = np.zeros(len(p), dtype=np.float32)
+    P[k_lo:k_hi] = np.where(zap[k_lo:k_hi], np.float32(1.0), (p[k_lo:k_hi] / mu).astype(np.float32))
+    return mu, P
+
+
+def sideband_spectra(P: np.ndarray, k_lo: int, k_hi: int, m: int, clip: float = 32.0) -> Tuple[np.ndarray, np.ndarray]:
+    """Step 3 at one size on one float32 row: (S float64 [nseg, M/2], norm
+    float64 [nseg] = ||x||_2 of each segment), by numpy.fft.rfft in float64."""
+    M = 1 << m
+    nseg = sideband_nseg(k_hi - k_lo, m)
+    if nseg == 0:
+        return np.zeros((0, M // 2)), np.zeros(0)
+    x = np.minimum(np.asarray(P[k_lo:k_hi], dtype=np.float32), np.float32(clip)).astype(np.float64) - 1.0
+    idx = (np.arange(nseg) * (M // 2))[:, None] + np.arange(M)[None, :]
+    seg = x[idx]
+    F = np.fft.rfft(seg, axis=1)[:, :M // 2]
+    return (F.real ** 2 + F.imag ** 2) / M, np.sqrt((seg * seg).sum(axis=1))
+
+
+def sideband_bound(S: np.ndarray, norm: np.ndarray, m: int) -> np.ndarray:
+    """What a float32 radix FFT may differ from S by: t = 16 u log2(M) ||x||_2 on
+    |F|, so (2 |F| t + t^2) / M on S (u = 2^-24)."""
+    M = 1 << m
+    t = 16.0 * 2.0 ** -24 * m * np.asarray(norm, dtype=np.float64)
+    t = t.reshape((-1,) + (1,) * (np.ndim(S) - 1)) if np.ndim(S) > 1 else t
+    return (2.0 * np.sqrt(np.asarray(S) * M) * t + t * t) / M
+
+
+def sideband_search(P: np.ndarray, k_lo: int, k_hi: int, m_lo: int = 5, m_hi: int = 13, j_min: int = 2,
+                    clip: float = 32.0, min_power: float = 30.0, dm_idx: int = 0) -> Dict:
+    """Steps 3 and 4 on one float32 row.  Returns per size m: best_S, best_j
+    (lowest j on a tie), bound (on best_S), gap (largest less second largest S)
+    and the events (dm_idx, m, seg, j, S) of S >= min_power."""
+    out = {"events": []}
+    for m in range(m_lo, m_hi + 1):
+        S, norm = sideband_spectra(P, k_lo, k_hi, m, clip)
+        if S.shape[0] == 0:
+            out[m] = {"best_S": np.zeros(0), "best_j": np.zeros(0, dtype=np.int64), "bound": np.zeros(0),
+                      "gap": np.zeros(0)}
+            continue
+        A = S[:, j_min:]
+        j = np.argmax(A, axis=1)  # the first of equal maxima
+        best = A[np.arange(len(j)), j]
+        if A.shape[1] > 1:
+            part = np.partition(A, A.shape[1] - 2, axis=1)
+            gap = part[:, -1] - part[:, -2]
+        else:
+            gap = np.full(len(j), np.inf)
+        out[m] = {"best_S": best, "best_j": j + j_min, "bound": sideband_bound(best, norm, m), "gap": gap}
+        for s in np.nonzero(best >= min_power)[0]:
+            out["events"].append((int(dm_idx), m, int(s), int(j[s] + j_min), float(best[s])))
+    return out
+
+
+def sideband_related(e, c0) -> bool:
+    """Step 5's two conditions, in exact integers."""
+    _, m, seg, j, _ = e
+    _, m0, seg0, j0, _ = c0
+    M, M0 = 1 << m, 1 << m0
+    c = seg * (M // 2) + M // 2
+    cc = seg0 * (M0 // 2) + M0 // 2
+    if abs(c - cc) > (M + M0) // 2:
+        return False
+    for r in range(1, 5):
+        if abs(r * j * M0 - j0 * M) <= r * M0 + M or abs(j * M0 - r * j0 * M) <= M0 + r * M:
+            return True
+    return False
+
+
+def sideband_cluster(events) -> List[Tuple[tuple, int, int, int]]:
+    """Step 5: [(leading event, members, dm_lo, dm_hi)] in descending S."""
+    ev = sorted((tuple(e) for e in events), key=lambda e: (-float(np.float32(e[4])), e[0], e[1], e[2]))
+    out: List[list] = []
+    for e in ev:
+        for c in out:
+            if sideband_related(e, c[0]):
+                c[1] += 1
+                c[2] = min(c[2], e[0])
+                c[3] = max(c[3], e[0])
+                break
+        else:
+            out.append([e, 1, e[0], e[0]])
+    return [tuple(c) for c in out]
