@@ -388,7 +388,10 @@ def py_distill(cands, cond):
 def harm_related(f0, freqs, nhs, tol, max_harm, frac):
     """HarmonicDistiller::condition: per later candidate (freqs, nhs) the
     number of (jj, kk), jj = 1..max_harm, kk = 1..(2^nh if frac else 1), with
-    1 - tol < kk f / (jj f0) < 1 + tol (tol as float32, the ratio in double)."""
+    1 - tol < kk f / (jj f0) < 1 + tol (the ratio in double; tol a float32 and
+    the bounds formed in float32, `double upper_tol = 1 + tolerance` with a
+    float tolerance, distiller.hpp:74-75 -- 1 - 1e-4f is 0.99989998, not the
+    0.9999000000025 of double arithmetic, and a ratio can fall between)."""
     f = np.asarray(freqs, dtype=np.float64)
     maxd = np.array([2.0 ** h if frac else 1.0 for h in nhs], dtype=np.float64)
     if not len(f):
@@ -396,7 +399,8 @@ def harm_related(f0, freqs, nhs, tol, max_harm, frac):
     jj = np.arange(1, int(max_harm) + 1, dtype=np.float64)
     kk = np.arange(1, int(maxd.max()) + 1, dtype=np.float64)
     r = (kk[None, None, :] * f[:, None, None]) / (jj[None, :, None] * f0)
-    hit = (r > 1 - f32(tol)) & (r < 1 + f32(tol)) & (kk[None, None, :] <= maxd[:, None, None])
+    lower, upper = float(np.float32(1) - np.float32(tol)), float(np.float32(1) + np.float32(tol))
+    hit = (r > lower) & (r < upper) & (kk[None, None, :] <= maxd[:, None, None])
     return hit.sum(axis=(1, 2))
 
 

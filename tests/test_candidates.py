@@ -5,6 +5,7 @@ import random
 import numpy as np
 import pytest
 
+import harmdistill_cases as hc
 from peasoup_amd.utils import reference as ref
 from peasoup_amd.utils.reference import Cand, acc_cond, f32, harm_cond, py_distill  # noqa: F401
 
@@ -49,6 +50,45 @@ def test_harmonic_distiller_matches_python(C, seed):
         assert [sig(c) for c in nat] == [sig(c) for c in py]
         if keep:
             assert [c.count_assoc() for c in nat] == [len(c.assoc) for c in py]
+
+
+@pytest.mark.parametrize("p", range(len(hc.PARAMS)))
+def test_harmonic_distiller_matches_python_on_device_trials(C, p):
+    """The trials of the device distiller's test (harmdistill_cases.py): the host HarmonicDistiller
+    equals reference.py_distill on each, in (level, S/N, frequency) and order -- so the device is
+    compared with a rule two host implementations agree on -- and the special trials are what
+    they claim, by the oracle."""
+    b = hc.batch(p)
+    nlev, tol, max_harm = hc.PARAMS[p]
+    assert int(C.kernels.harm_cap) == hc.HARM_CAP and (b["nlev"], b["tol"], b["max_harm"]) == (nlev, tol, max_harm)
+    hd = C.HarmonicDistiller(tol, max_harm, False, True)
+    sizes = {}
+    for k, (kind, lv) in enumerate(zip(b["kind"], b["trials"])):
+        tup = hc.tuples(lv)
+        assert len(lv) == nlev + 1 and all(np.all(np.diff(idx) > 0) and (len(idx) == 0 or 0 < idx[0]) for idx, _ in lv)
+        assert all(len(idx) == 0 or int(idx[-1]) < 1 << 29 for idx, _ in lv)
+        snr = [t[4] for t in tup]
+        assert (len(set(snr)) < len(snr)) == (kind == "tie"), kind  # a tie sends the trial to the host
+        exp = hc.oracle(p, k)
+        nat = [(c.nh, c.snr, c.freq) for c in hd.distill(to_native(C, tup))]
+        if kind != "tie":  # (the order of equal S/N is the sort's, not the rule's)
+            assert nat == exp, (p, kind)
+        sizes[kind] = (len(tup), len(exp))
+        if kind == "related":
+            assert len(exp) == 1 and exp[0][1] == max(snr) and len(tup) >= 7
+        if kind == "unrelated":
+            assert len(exp) == len(tup) >= 65  # more than one 64-candidate block, untouched by the oracle
+        if kind == "top":
+            assert int(lv[nlev][0][-1]) == (1 << 29) - 1
+        if kind == "edges":
+            f0 = max(tup, key=lambda t: t[4])
+            assert f0[3] == 0
+            rest = [(h, float(np.float32(i * hc.FACTOR[h]))) for h, i in b["planted"][k]]
+            n = ref.harm_related(f0[5], [f for _, f in rest], [h for h, _ in rest], tol, max_harm, True)
+            assert (n > 0).any() and (n == 0).any(), (p, n)  # both outcomes among the planted ones
+            assert max(h for h, _ in rest) == nlev
+    assert [sizes[f"size{n}"][0] for n in hc.SIZES] == hc.SIZES and sizes["empty"] == (0, 0)
+    assert all(sizes[f"size{n}"][1] < n for n in hc.SIZES if n >= 63)  # the relation removed candidates
 
 
 @pytest.mark.parametrize("seed", [3, 4])

@@ -1,12 +1,21 @@
 """Per-trial harmonic distillation on the device (kern::harm_distill_batch,
 csrc/kernels/harmdistill.hip) against the host HarmonicDistiller
 (include/transforms/distiller.hpp:63-108 semantics, csrc/src/candidates.cpp),
-and the search engine with device distillation against host distillation."""
+and the search engine with device distillation against host distillation.
+
+test_harm_distill_levels_tolerances_and_edges runs the trials of harmdistill_cases.py against the
+Python oracle: sizes 1 .. harm_cap (both kernel instances, the bitonic sort's padding, whole and
+part 64-blocks of the greedy scan), an all-related trial (step 3 (iii) clears every later word), an
+unrelated one (no relation bit), idx 2^29 - 1 at level nlev (the idx | level << 29 packing), ratios
+planted on the edges of (1 - tol, 1 + tol) (harm_related's prefilter and exact test) and a tie (the
+hand-off to the host), at level counts 0, 1, 2, 4, 5."""
 import os
 
 import numpy as np
 import pytest
 import torch
+
+import harmdistill_cases as hc
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -105,6 +114,58 @@ def test_harm_distill_matches_host(C):
         total += cnt
     assert int(d_tot.item()) == total
     assert ndev >= 10, ndev  # most trials distilled on the device
+
+
+@pytest.mark.parametrize("p", range(len(hc.PARAMS)))
+def test_harm_distill_levels_tolerances_and_edges(C, p):
+    """Level counts 0, 1, 2, 4, 5, every (tol, max_harm) the issue names, on the trials of
+    harmdistill_cases.py (what each is for: its docstring), against reference.py_distill --
+    test_candidates.py shows the host distiller equal to it on the same trials.  Equal in
+    (level, S/N bits, float32 frequency) and order; the tie trial goes to the host."""
+    K = C.kernels
+    b = hc.batch(p)
+    nlev, tol, max_harm = hc.PARAMS[p]
+    assert int(K.harm_cap) == hc.HARM_CAP
+    nt = len(b["trials"])
+    clust, segtab, off = [], np.zeros((nt, 8, 2), np.uint32), 0
+    for k, lv in enumerate(b["trials"]):
+        for h, (idx, snr) in enumerate(lv):
+            segtab[k, h] = (off, len(idx))
+            clust.append(np.stack([idx.view(np.uint32), snr.view(np.uint32)], axis=1))
+            off += len(idx)
+    clust = np.concatenate(clust)
+    d_clust = torch.from_numpy(clust.reshape(-1).view(np.int32).copy()).to(dev)
+    d_seg = torch.from_numpy(segtab.reshape(-1).view(np.int32).copy()).to(dev)
+    d_out = torch.zeros(2 * off, dtype=torch.int32, device=dev)
+    d_ttab = torch.full((2 * nt,), -1, dtype=torch.int32, device=dev)
+    d_tot = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream().cuda_stream
+    K.harm_distill_batch(d_clust.data_ptr(), d_seg.data_ptr(), nt, nlev, hc.FACTOR, tol, float(max_harm),
+                         d_out.data_ptr(), d_ttab.data_ptr(), d_tot.data_ptr(), s)
+    torch.cuda.synchronize()
+    ttab = d_ttab.cpu().numpy().view(np.uint32).reshape(nt, 2)
+    out = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    total, spans = 0, []
+    for k, kind in enumerate(b["kind"]):
+        first, cnt = int(ttab[k, 0]), int(ttab[k, 1])
+        if kind == "tie":
+            assert (first, cnt) == (0, HOST), (kind, first, hex(cnt))
+            continue
+        exp = hc.oracle(p, k)
+        assert cnt == len(exp), (kind, cnt, len(exp))
+        got = out[first:first + cnt]
+        lev = (got[:, 0] >> 29).astype(np.int64)
+        idx = (got[:, 0] & ((1 << 29) - 1)).astype(np.int64)
+        frq = np.array([np.float32(int(i) * hc.FACTOR[h]) for i, h in zip(idx, lev)], np.float32)
+        assert lev.tolist() == [e[0] for e in exp], kind
+        assert np.array_equal(got[:, 1], np.array([e[1] for e in exp], np.float32).view(np.uint32)), kind
+        assert np.array_equal(frq.view(np.uint32), np.array([e[2] for e in exp], np.float32).view(np.uint32)), kind
+        total += cnt
+        if cnt:
+            spans.append((first, cnt))
+    assert int(d_tot.item()) == total
+    spans.sort()  # packed: disjoint ranges filling [0, total)
+    assert [a for a, _ in spans] == np.r_[0, np.cumsum([n for _, n in spans])][:-1].tolist()
 
 
 def _search(C, trial, nsamps, accs, cluster, distill):

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from peakcluster_cases import chunked_records  # the record format, shared with the path tests
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 
@@ -20,28 +22,6 @@ def _segment(rng, n, span, ties):
     if ties:
         snr = np.round(snr * 2) / 2  # equal S/N neighbours: the strict '>' rule
     return idx, snr.astype(np.float32)
-
-
-def chunked_records(segs, rng):
-    """Records as harmonic_peaks_batch emits them: per segment, runs of
-    idx-ascending crossings of one 64-bin group, each behind its descriptor
-    {0x80000000 | count << 16 | segment, first idx, position}; chunks in any
-    order (kernels.hpp kPeakChunk)."""
-    chunks = []
-    for s, (idx, snr) in segs.items():
-        grp = idx >> 6
-        cuts = np.flatnonzero(np.diff(grp)) + 1
-        for a, b in zip(np.r_[0, cuts], np.r_[cuts, len(idx)]):
-            chunks.append((s, idx[a:b], snr[a:b]))
-    order = rng.permutation(len(chunks))
-    rows, pos = [], 0
-    for k in order:
-        s, ci, cs = chunks[k]
-        c = len(ci)
-        rows.append(np.array([[0x80000000 | (c << 16) | s, int(ci[0]), pos + 1]], np.uint32))
-        rows.append(np.stack([np.full(c, s, np.uint32), ci.view(np.uint32), cs.view(np.uint32)], axis=1))
-        pos += 1 + c
-    return np.concatenate(rows)
 
 
 @pytest.mark.parametrize("gap", [30, 5, 1])
