@@ -131,6 +131,7 @@ void bind_inject(py::module_& m);   // bind_inject.cpp
 void bind_bopt(py::module_& m);     // bind_bopt.cpp
 void bind_jerk(py::module_& m);     // bind_jerk.cpp
 void bind_orbit(py::module_& m);    // bind_orbit.cpp
+void bind_orbopt(py::module_& m);   // bind_orbopt.cpp
 void bind_sideband(py::module_& m); // bind_sideband.cpp
 
 PYBIND11_MODULE(_C, m) {
@@ -714,6 +715,7 @@ PYBIND11_MODULE(_C, m) {
   bind_bopt(m);
   bind_jerk(m);
   bind_orbit(m);
+  bind_orbopt(m);
   bind_sideband(m);
 
   py::module_ k = m.def_submodule("kernels", "raw HIP kernel launchers (addresses + stream handles)");

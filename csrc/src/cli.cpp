@@ -6,6 +6,7 @@
 #include "psoup/inject.hpp"
 #include "psoup/jerk.hpp"
 #include "psoup/orbit.hpp"
+#include "psoup/orbopt.hpp"
 #include "psoup/sideband.hpp"
 #include "psoup/psrfits.hpp"
 #include "psoup/foldcube.hpp"
@@ -886,6 +887,52 @@ bool parse_orbit_cmdline(OrbitCmdLineOptions& o, const std::vector<std::string>&
   }
   if (a.npdmp < 0 || a.limit < 0) {
     std::cerr << "Error: --npdmp and --limit must be non-negative" << std::endl;
+    return false;
+  }
+  return true;
+}
+
+std::string default_oopt_output_filename() {
+  char buf[128];
+  std::time_t t = std::time(nullptr);
+  std::strftime(buf, sizeof(buf), "%Y-%m-%d-%H:%M_orbopt.oopt", std::gmtime(&t));
+  return std::string(buf);
+}
+
+bool parse_oopt_cmdline(OrbOptCmdLineOptions& a, const std::vector<std::string>& argv, bool* exit_now) {
+  a.outfilename = default_oopt_output_filename();
+  std::vector<Spec> specs = {
+      val_s("i", "inputfile", "File to process (.fil)", a.infilename, true),
+      val_s("c", "candfile", "Candidates: lines `period_s dm acc pb_s a1_ls phase` (an orbsearch output)",
+            a.candfilename, true),
+      val_s("o", "outfilename", "The output filename", a.outfilename),
+      val_s("k", "killfile", "Channel mask file", a.killfilename),
+      val_n("t", "num_threads", "The number of GPUs to use: only 1 (one device)", a.max_num_threads),
+      val_u("", "fft_size", "Span the candidates were found with (defaults to lower power of two)", a.size),
+      val_n("", "nbins", "Phase bins (2..256)", a.nbins),
+      val_n("", "nints", "Subintegrations (1..64; nints * nbins <= 16384)", a.nints),
+      val_n("", "npb", "Orbital periods of the local grid (odd)", a.npb),
+      val_n("", "na1", "Semi-major axes of the local grid (odd)", a.na1),
+      val_n("", "nphase", "Orbital phases of the local grid (odd)", a.nphase),
+      val_d("pb_step", "Step in orbital period, s (0 = about half a phase bin)", a.pb_step),
+      val_d("a1_step", "Step in a sin i / c, light-seconds (0 = about half a phase bin)", a.a1_step),
+      val_d("phase_step", "Step in orbital phase, turns (0 = about half a phase bin)", a.phase_step),
+      val_n("", "np", "Period-drift trials (odd, 1..257)", a.np),
+      val_d("p_step", "Bins of drift across the fold per trial", a.p_step),
+      val_n("", "limit", "At most this many candidates from the top of the file", a.limit),
+      sw("v", "verbose", "verbose mode: one line per candidate", a.verbose),
+  };
+  if (!run_parser(specs, argv,
+                  "Peasoup orbopt extension - refine orbit candidates by folding on a local template grid (one device)",
+                  nullptr, exit_now))
+    return false;
+  if (exit_now && *exit_now) return true;
+  if (a.max_num_threads != 1) {
+    std::cerr << "Error: orbopt runs on one device (-t 1); multi-GPU runs are not supported" << std::endl;
+    return false;
+  }
+  if (a.limit < 0) {
+    std::cerr << "Error: --limit must be non-negative" << std::endl;
     return false;
   }
   return true;

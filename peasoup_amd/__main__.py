@@ -12,7 +12,8 @@ fits [fits2fil flags]`` for the conversion of a search-mode PSRFITS file, ``pyth
 [filinject flags]`` for the injection of dispersed pulsars and bursts into a filterbank, ``python -m peasoup_amd jerk
 [jerksearch flags]`` for the acceleration search repeated over jerk trials, ``python -m peasoup_amd orb
 [orbsearch flags]`` for the one repeated over circular-orbit templates, ``python -m peasoup_amd sb
-[sbsearch flags]`` for the sideband search for short orbits) -- the peasoup CLI as a
+[sbsearch flags]`` for the sideband search for short orbits, ``python -m peasoup_amd oopt [orbopt flags]``
+for the refinement of orbit candidates on a local template grid) -- the peasoup CLI as a
 torchrun-compatible, one-process-per-GPU program:
 
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -102,6 +103,8 @@ def main(argv=None) -> int:
         return _main_orbit(["orbsearch"] + argv[2:])
     if len(argv) > 1 and argv[1] == "sb":
         return _main_sb(["sbsearch"] + argv[2:])
+    if len(argv) > 1 and argv[1] == "oopt":
+        return _main_oopt(["orbopt"] + argv[2:])
     argv[0] = "peasoup"
     ok, exit_now, args = _C.parse_cmdline(argv)
     if not ok:
@@ -390,6 +393,26 @@ def _main_orbit(argv) -> int:
     if res is not None and args.search.verbose:
         print(f"orbsearch: {len(res.candidates)} candidates from {res.template_trials} DM-template trials "
               f"({res.accel_trials} acceleration trials) to {args.outfilename}")
+    return 0
+
+
+def _main_oopt(argv) -> int:
+    from . import _C
+    from .models.orbopt import print_records, run_orbit_optimise
+
+    ok, exit_now, args = _C.parse_oopt_cmdline(argv)
+    if not ok:
+        print("Failed to parse command line arguments.", file=sys.stderr)
+        return 1
+    if exit_now:
+        return 0
+    try:
+        res = run_orbit_optimise(args)
+    except BaseException as e:  # noqa: BLE001 - same teardown policy as the search
+        _fail_hard("oopt", e)
+    if res is not None and args.verbose:
+        print_records(res)
+        print(f"orbopt: {len(res.records)} candidates to {args.outfilename}")
     return 0
 
 

@@ -65,6 +65,6 @@ if __name__ == "__main__":
     if "--sanitize" in sys.argv:
         san = sys.argv[sys.argv.index("--sanitize") + 1]
     target = "psoup_unit_tests"
-    if "--target" in sys.argv:  # psoup_rfi_unit_tests, psoup_opt_unit_tests, psoup_scrunch_unit_tests, psoup_digi_unit_tests, psoup_fits_unit_tests, psoup_bopt_unit_tests, psoup_inject_unit_tests, psoup_jerk_unit_tests, psoup_orbit_unit_tests, psoup_sideband_unit_tests
+    if "--target" in sys.argv:  # psoup_rfi_unit_tests, psoup_opt_unit_tests, psoup_scrunch_unit_tests, psoup_digi_unit_tests, psoup_fits_unit_tests, psoup_bopt_unit_tests, psoup_inject_unit_tests, psoup_jerk_unit_tests, psoup_orbit_unit_tests, psoup_sideband_unit_tests, psoup_orbopt_unit_tests
         target = sys.argv[sys.argv.index("--target") + 1]
     build(verbose="-v" in sys.argv, clean="--clean" in sys.argv, sanitize=san, sanitize_target=target)

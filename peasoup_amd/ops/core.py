@@ -1206,6 +1206,98 @@ def orbit_resample(trials: torch.Tensor, n: int, templates, tsamp: float, nrow: 
     return out
 
 
+# ---------------------------------------------------------------- orbopt ----
+def orbopt_fold(trials: torch.Tensor, n: int, G, quant, nints: int, nbins: int, row_of=None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The orbopt_fold kernel (csrc/include/psoup/orbopt.hpp, step 2): uint8
+    rows ``trials`` [nrows, row_stride]; candidate c folds the first ``n``
+    samples of row ``row_of[c]`` (default: row c) with the phase step ``G[c]``
+    at its quantised templates ``quant[c]`` (K triples (W, F, Aq), the same K
+    for every candidate).  Returns ``out`` int32 [ncand, K, nints, nbins],
+    zeroed and written here.  ``trials`` may be a view whose rows are further
+    apart than they are long.  Equals ``utils.reference.orbopt_fold`` exactly."""
+    if not trials.is_cuda or trials.dtype != torch.uint8:
+        raise ValueError("trials must be a uint8 HIP (cuda) tensor")
+    if trials.dim() != 2:
+        raise ValueError("trials must be [nrows, row_stride]")
+    nrows, row_stride = int(trials.shape[0]), int(trials.stride(0))
+    if trials.stride(1) != 1:
+        raise ValueError("the samples of a row must be contiguous")
+    G = [int(g) for g in G]
+    ncand = len(G)
+    rows = list(range(ncand)) if row_of is None else [int(r) for r in row_of]
+    if ncand < 1 or len(quant) != ncand or len(rows) != ncand or any(not 0 <= r < nrows for r in rows):
+        raise ValueError("need one G, one row in [0, nrows) and one template list per candidate")
+    K = len(quant[0])
+    if K < 1 or any(len(q) != K for q in quant):
+        raise ValueError("every candidate needs the same number K >= 1 of templates")
+    if not 1 <= int(n) <= int(trials.shape[1]):
+        raise ValueError("need 1 <= n <= the row length")
+    q = [tuple(int(v) for v in t) for c in quant for t in c]
+    if out is None:
+        out = torch.empty((ncand, K, nints, nbins), dtype=torch.int32, device=trials.device)
+    _check(out, torch.int32, "out")
+    if tuple(out.shape) != (ncand, K, nints, nbins) or not out.is_contiguous():
+        raise ValueError("out must be contiguous [ncand, K, nints, nbins]")
+    dev = trials.device
+    packed = np.array([[t[0], t[1], t[2] & 0xFFFFFFFFFFFFFFFF] for t in q], dtype=np.uint64).reshape(-1, 3)
+    d_q = torch.from_numpy(packed.view(np.int64)).to(dev)  # freed stream-ordered by torch's allocator
+    d_G = torch.from_numpy(np.array(G, dtype=np.uint64).view(np.int64)).to(dev)
+    d_rows = torch.tensor(rows, dtype=torch.int32, device=dev)
+    in_bytes = (nrows - 1) * row_stride + int(trials.shape[1])
+    _C.orbopt_fold_raw(trials.data_ptr(), row_stride, in_bytes, rows, d_rows.data_ptr(), d_G.data_ptr(), q,
+                       d_q.data_ptr(), K, int(n), int(nints), int(nbins), _orbit_table(dev).data_ptr(), out.data_ptr(),
+                       _s())
+    return out
+
+
+def orbopt_search(fold: torch.Tensor, hits: torch.Tensor, m: torch.Tensor, st) -> Dict[str, torch.Tensor]:
+    """The orbopt_search kernel (orbopt.hpp, step 4): ``fold`` int32 [ncand, K,
+    nints, nbins], ``hits`` int32 [ncand, nints, nbins], ``m`` int32 [ncand]
+    on the device, ``st`` the drift table [np, nints] on the host with every
+    shift in [0, nbins).  Returns device tensors best_val, best_idx, centre
+    int32 [ncand, nw], tcurve int32 [ncand, nw, K], msum int64 [ncand, K].
+    Equals ``utils.reference.orbopt_search`` exactly."""
+    for t, name in ((fold, "fold"), (hits, "hits"), (m, "m")):
+        _check(t, torch.int32, name)
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if fold.dim() != 4:
+        raise ValueError("fold must be [ncand, K, nints, nbins]")
+    ncand, K, nints, nbins = (int(v) for v in fold.shape)
+    st = np.ascontiguousarray(st, dtype=np.int32)
+    if tuple(hits.shape) != (ncand, nints, nbins) or tuple(m.shape) != (ncand,) or st.ndim != 2 or st.shape[1] != nints:
+        raise ValueError("hits must be [ncand, nints, nbins], m [ncand] and st [np, nints]")
+    np_ = int(st.shape[0])
+    nw = int(_C.oopt_nwidths(nbins))
+    dev = fold.device
+    d_st = torch.from_numpy(st).to(dev)
+    keys = torch.empty((ncand, nw), dtype=torch.int64, device=dev)
+    out = {"best_val": torch.empty((ncand, nw), dtype=torch.int32, device=dev),
+           "best_idx": torch.empty((ncand, nw), dtype=torch.int32, device=dev),
+           "centre": torch.empty((ncand, nw), dtype=torch.int32, device=dev),
+           "tcurve": torch.empty((ncand, nw, K), dtype=torch.int32, device=dev),
+           "msum": torch.empty((ncand, K), dtype=torch.int64, device=dev)}
+    _C.orbopt_search_raw(fold.data_ptr(), hits.data_ptr(), m.data_ptr(), [int(v) for v in st.ravel()], d_st.data_ptr(),
+                         ncand, K, nints, nbins, np_, keys.data_ptr(), out["best_val"].data_ptr(),
+                         out["best_idx"].data_ptr(), out["tcurve"].data_ptr(), out["centre"].data_ptr(),
+                         out["msum"].data_ptr(), _s())
+    return out
+
+
+def orbit_optimise(fb, candidates, fft_size: int, **params):
+    """orbopt on a resident ``_C.DeviceFilterbank`` whose DM list holds every
+    candidate's DM: ``candidates`` are (period, dm, acc, pb, a1, phase) tuples,
+    ``params`` the fields of ``_C.OrbOptParams`` (nbins, nints, npb, na1, nphase,
+    np, p_step, pb_step, a1_step, phase_step) and optionally ``batch_bytes``.
+    Returns one record dict per candidate, as ``utils.reference.orbit_optimise``."""
+    kw = {}
+    if "batch_bytes" in params:
+        kw["batch_bytes"] = int(params.pop("batch_bytes"))
+    opt = _C.OrbitOptimiser(_C.OrbOptParams(**params), fb, int(fft_size), _s(), **kw)
+    return opt.optimise([tuple(float(v) for v in c) for c in candidates])
+
+
 # -------------------------------------------------------------- sideband ----
 _SB_TWIDDLES: Dict = {}
 SB_EVENT_DTYPE = [("dm_idx", "<i4"), ("m", "<i4"), ("seg", "<i4"), ("j", "<i4"), ("S", "<f4")]  # SbEvent

@@ -338,6 +338,93 @@ class FoldOptFile:
         return out
 
 
+# ---------------------------------------------------------------- orbopt ----
+OOPT_MAGIC = b"PSOOPT01"
+_OOPT_HEADER = struct.Struct("<8s8IQ2d")   # magic, ncand nints nbins npb na1 nphase np nw, n, tsamp p_step
+_OOPT_CAND = struct.Struct("<dff12d8I2q")  # period dm acc | pb a1 phase dpb da1 dph snr snr_in opt_period opt_pb opt_a1
+#                                            opt_phase | opt_width opt_bin opt_k opt_l flags npb na1 nphase | m v1
+OOPT_HEADER_FIELDS = ("ncand", "nints", "nbins", "npb", "na1", "nphase", "np", "nw", "n", "tsamp", "p_step")
+_OOPT_SCALARS = ("period", "dm", "acc", "pb", "a1", "phase", "dpb", "da1", "dph", "snr", "snr_in", "opt_period", "opt_pb",
+                 "opt_a1", "opt_phase", "opt_width", "opt_bin", "opt_k", "opt_l", "flags", "npb", "na1", "nphase", "m",
+                 "v1")
+
+
+def _oopt_arrays(h: Dict, K: int):
+    nw, ni, nb = (int(h[k]) for k in ("nw", "nints", "nbins"))
+    return (("best_val", "<i4", (nw,)), ("best_idx", "<i4", (nw,)), ("centre", "<i4", (nw,)), ("tcurve", "<i4", (nw, K)),
+            ("msum", "<i8", (K,)), ("hits", "<i4", (ni, nb)), ("fold", "<i4", (ni, nb)), ("profile", "<i4", (nb,)))
+
+
+def write_orbopt_file(path: str, header: Dict, records: List[Dict]) -> None:
+    """Writes an orbopt result file byte for byte as the native
+    ``write_orbopt_file`` (csrc/src/orbopt_host.cpp): little-endian
+    ``PSOOPT01``, uint32 ncand nints nbins npb na1 nphase np nw, uint64 n,
+    double tsamp p_step (64 bytes); per candidate double period, float dm,
+    float acc, double pb a1 phase dpb da1 dph snr snr_in opt_period opt_pb
+    opt_a1 opt_phase, uint32 opt_width opt_bin opt_k opt_l flags npb na1 nphase
+    (the counts used, K their product), int64 m v1 (160 bytes), then int32
+    best_val[nw], best_idx[nw], centre[nw], tcurve[nw][K], int64 msum[K], int32
+    hits[nints][nbins], fold[nints][nbins], profile[nbins].  ``header`` needs
+    every field but ncand.  Written to a temporary file, then renamed."""
+    import os
+
+    h = dict(header, ncand=len(records))
+    blob = [_OOPT_HEADER.pack(OOPT_MAGIC, *(int(h[k]) for k in OOPT_HEADER_FIELDS[:9]), float(h["tsamp"]),
+                              float(h["p_step"]))]
+    for i, r in enumerate(records):
+        blob.append(_OOPT_CAND.pack(*(float(r[k]) for k in _OOPT_SCALARS[:15]), *(int(r[k]) for k in _OOPT_SCALARS[15:])))
+        K = int(r["npb"]) * int(r["na1"]) * int(r["nphase"])
+        for name, dt, shape in _oopt_arrays(h, K):
+            a = np.ascontiguousarray(r[name], dtype=dt)
+            if a.shape != shape:
+                raise ValueError(f"orbopt file: candidate {i}: {name} has the wrong shape")
+            blob.append(a.tobytes())
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(b"".join(blob))
+    os.replace(tmp, path)
+
+
+class OrbOptFile:
+    """Reader of an orbopt result file (``bin/orbopt`` / ``python -m
+    peasoup_amd oopt``): ``len``, ``header``, ``candidate(i)``."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._buf = open(path, "rb").read()
+        if len(self._buf) < _OOPT_HEADER.size or self._buf[:8] != OOPT_MAGIC:
+            raise ValueError(f"{path}: not an orbopt result file")
+        self.header: Dict = dict(zip(OOPT_HEADER_FIELDS, _OOPT_HEADER.unpack_from(self._buf, 0)[1:]))
+        # the records differ in size with their template counts: walk them once
+        self._offsets = []
+        o = _OOPT_HEADER.size
+        for _ in range(int(self.header["ncand"])):
+            if o + _OOPT_CAND.size > len(self._buf):
+                raise ValueError(f"{path}: truncated orbopt result file")
+            v = _OOPT_CAND.unpack_from(self._buf, o)
+            K = v[20] * v[21] * v[22]
+            self._offsets.append(o)
+            o += _OOPT_CAND.size + sum(np.dtype(dt).itemsize * int(np.prod(sh)) for _, dt, sh in
+                                       _oopt_arrays(self.header, K))
+        if o != len(self._buf):
+            raise ValueError(f"{path}: truncated orbopt result file")
+
+    def __len__(self) -> int:
+        return int(self.header["ncand"])
+
+    def candidate(self, i: int) -> Dict:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        o = self._offsets[i]
+        out = dict(zip(_OOPT_SCALARS, _OOPT_CAND.unpack_from(self._buf, o)))
+        o += _OOPT_CAND.size
+        for name, dt, shape in _oopt_arrays(self.header, out["npb"] * out["na1"] * out["nphase"]):
+            cnt = int(np.prod(shape))
+            out[name] = np.frombuffer(self._buf, dt, cnt, o).reshape(shape).copy()
+            o += cnt * np.dtype(dt).itemsize
+        return out
+
+
 # --------------------------------------------------------- burst cutouts ----
 BURST_MAGIC = b"PSBRST01"
 _BURST_HEADER = struct.Struct("<8s6IQ3d")  # magic, ncand ntime nsub ndm nchans nbits, nsamps, tsamp fch1 foff

@@ -162,6 +162,28 @@ def p_pdot_panel(rec: Dict) -> np.ndarray:
     return _opt_snr_plane(rec, rec["ppd"]).T.copy()
 
 
+def orbit_surface_panel(rec: Dict) -> Tuple[np.ndarray, np.ndarray]:
+    """Two slices of an orbopt record's S/N surface through the optimum
+    template: (float64 [na1, npb] at the optimum's orbital phase, float64 [na1,
+    nphase] at the optimum's orbital period), each the S/N (orbopt.hpp, step 5)
+    of ``tcurve`` with the template's own ``msum``, maximised over the widths;
+    a1 runs along y."""
+    npb, na1, nph = int(rec["npb"]), int(rec["na1"]), int(rec["nphase"])
+    nbins = int(np.asarray(rec["profile"]).shape[0])
+    tc = np.asarray(rec["tcurve"], dtype=np.float64)                       # [nw, K]
+    v = float(rec["v1"]) / nbins
+    if not v > 0:
+        snr = np.zeros(tc.shape[1], dtype=np.float64)
+    else:
+        w = (2.0 ** np.arange(tc.shape[0]))[:, None]
+        snr = ((tc - w * np.asarray(rec["msum"], dtype=np.float64)[None, :] / nbins) /
+               np.sqrt(v * w * (1.0 - w / nbins))).max(axis=0)
+    cube = snr.reshape(npb, na1, nph)
+    k = int(rec["opt_k"])
+    kp, kb = k % nph, k // nph // na1
+    return cube[:, :, kp].T.copy(), cube[kb].copy()
+
+
 def burst_dm_curve_panel(rec: Dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
     """(dms float64 [ndm], S/N float64 [ndm], dmf float64 [nfine], S/N float64
     [nfine]) of a burstopt record: for every coarse DM row and every fine DM

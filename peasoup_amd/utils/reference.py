@@ -3066,3 +3066,245 @@ def sideband_cluster(events) -> List[Tuple[tuple, int, int, int]]:
         else:
             out.append([e, 1, e[0], e[0]])
     return [tuple(c) for c in out]
+
+
+# ---------------------------------------------------------------- orbopt ----
+# The oracle of csrc/include/psoup/orbopt.hpp, written from its definition in
+# Python ints, int64 and float64; the fold is built on orbit_shift above.
+OOPT_MAX_TEMPLATES = 4096
+
+
+def orbopt_check_params(nbins: int = 64, nints: int = 16, npb: int = 9, na1: int = 9, nphase: int = 9, np_: int = 33,
+                        p_step: float = 1.0, pb_step: float = 0.0, a1_step: float = 0.0, phase_step: float = 0.0) -> None:
+    if not 2 <= nbins <= 256:
+        raise ValueError("orbopt: nbins must be in 2..256")
+    if not 1 <= nints <= 64:
+        raise ValueError("orbopt: nints must be in 1..64")
+    if min(npb, na1, nphase) < 1 or npb % 2 == 0 or na1 % 2 == 0 or nphase % 2 == 0:
+        raise ValueError("orbopt: an even count (--npb, --na1 and --nphase must be odd and at least 1)")
+    if not 1 <= np_ <= 257 or np_ % 2 == 0:
+        raise ValueError("orbopt: an even count (--np must be odd and in 1..257)")
+    if npb * na1 * nphase > OOPT_MAX_TEMPLATES:
+        raise ValueError("orbopt: more than 4096 templates per candidate")
+    if not all(math.isfinite(v) and v >= 0 for v in (p_step, pb_step, a1_step, phase_step)):
+        raise ValueError("orbopt: the steps must be finite and non-negative")
+
+
+def orbopt_grid(cand, n: int, tsamp: float, nbins: int = 64, npb: int = 9, na1: int = 9, nphase: int = 9,
+                pb_step: float = 0.0, a1_step: float = 0.0, phase_step: float = 0.0, k: int = 0) -> Dict:
+    """Step 1 and G for ``cand`` = (period, dm, acc, pb, a1, phase): dict(npb,
+    na1, nphase, dpb, da1, dph, G, templates [(pb, a1, ph)] after the sign fold,
+    quant [(W, F, Aq)]).  Raises ValueError naming ``candidate k``."""
+    P, dm, acc, pb0, a10, ph0 = (float(v) for v in cand)
+    ts = float(np.float32(tsamp))
+    who = f"orbopt: candidate {k}"
+    if int(n) > ORBIT_MAX_SPAN:
+        raise ValueError("orbopt: series longer than 2^26 samples")
+    if not math.isfinite(P) or P < 2.0 * ts:
+        raise ValueError(who + ": the period is not finite or below 2 tsamp")
+    if not math.isfinite(dm) or dm < 0:
+        raise ValueError(who + ": a non-finite or negative DM")
+    if not all(math.isfinite(v) for v in (acc, pb0, a10, ph0)):
+        raise ValueError(who + ": orbit: a non-finite value")
+    T = float(int(n)) * ts
+    nb = float(nbins)
+    da1 = float(a1_step) if a1_step > 0 else P / (2.0 * nb)
+    if phase_step > 0:
+        dph = float(phase_step)
+    elif a10 == 0.0:
+        dph, nphase = 0.0, 1
+    else:
+        dph = min(1.0 / 16.0, P / ((4.0 * math.pi) * abs(a10) * nb))
+    if pb_step > 0:
+        dpb = float(pb_step)
+    elif a10 == 0.0:
+        dpb, npb = 0.0, 1
+    else:
+        dpb = min(pb0 / 16.0, (pb0 * pb0 * P) / ((4.0 * math.pi) * abs(a10) * T * nb))
+    G = int(np.rint(math.ldexp(ts / P, 64)))
+    tmpl, quant = [], []
+    for kb in range(npb):
+        for ka in range(na1):
+            for kp in range(nphase):
+                pb = pb0 + float(kb - npb // 2) * dpb
+                a1 = a10 + float(ka - na1 // 2) * da1
+                ph = ph0 + float(kp - nphase // 2) * dph
+                if a1 < 0.0:
+                    a1, ph = -a1, ph + 0.5
+                try:
+                    quant.append(orbit_quantise(pb, a1, ph, ts))
+                    if orbit_beta(pb, a1) > 0.9:
+                        raise ValueError("orbit: a template moves more than 0.9 samples per sample")
+                except ValueError as e:
+                    raise ValueError(f"{who}: grid template {len(tmpl)}: {e}") from None
+                tmpl.append((pb, a1, ph))
+    return {"npb": npb, "na1": na1, "nphase": nphase, "dpb": dpb, "da1": da1, "dph": dph, "G": G, "templates": tmpl,
+            "quant": quant}
+
+
+def orbopt_bins(n: int, G: int, nints: int, nbins: int) -> np.ndarray:
+    """The flat cell j(i) * nbins + b(i) of every sample, int64 [n]."""
+    i = np.arange(int(n), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        phi = i * np.uint64(G)
+    b = ((phi >> np.uint64(32)) * np.uint64(nbins)) >> np.uint64(32)
+    j = (i * np.uint64(nints)) // np.uint64(n)
+    return (j * np.uint64(nbins) + b).astype(np.int64)
+
+
+def orbopt_hits(n: int, G: int, nints: int, nbins: int) -> np.ndarray:
+    return np.bincount(orbopt_bins(n, G, nints, nbins), minlength=nints * nbins).astype(np.int32).reshape(nints, nbins)
+
+
+def orbopt_fold_plain(y: np.ndarray, n: int, G: int, nints: int, nbins: int) -> np.ndarray:
+    """The plain fold of one (already resampled) row's first n samples: int32 [nints, nbins], modulo 2^32."""
+    cell = orbopt_bins(n, G, nints, nbins)
+    s = np.zeros(nints * nbins, dtype=np.int64)
+    np.add.at(s, cell, np.asarray(y[:int(n)], dtype=np.int64))
+    return (s & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(nints, nbins)
+
+
+def orbopt_fold(x: np.ndarray, n: int, G: int, quant, nints: int, nbins: int) -> np.ndarray:
+    """Step 2 for one row: int32 [K, nints, nbins]."""
+    x = np.asarray(x)
+    n = int(n)
+    cell = orbopt_bins(n, G, nints, nbins)
+    i = np.arange(n, dtype=np.int64)
+    out = np.zeros((len(quant), nints * nbins), dtype=np.int64)
+    for k, q in enumerate(quant):
+        src = np.clip(i + orbit_shift(n, q), 0, n - 1)
+        out[k] = np.bincount(cell, weights=x[src].astype(np.float64), minlength=nints * nbins).astype(np.int64)
+    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(len(quant), nints, nbins)
+
+
+def orbopt_moments(x: np.ndarray, n: int, k: int = 0) -> Tuple[int, int]:
+    """Step 3's (m, V1) in Python ints; refuses candidate k at the int32 bound."""
+    n = int(n)
+    v = np.asarray(x[:n], dtype=np.int64)
+    m = (int(v.sum()) + n // 2) // n
+    v1 = int(((v - m) ** 2).sum())
+    if max(m, 255 - m) * n >= 2 ** 31:
+        raise ValueError(f"orbopt: candidate {k}: max(m, 255 - m) * n >= 2^31")
+    return m, v1
+
+
+def orbopt_drift_table(nints: int, nbins: int, np_: int, p_step: float = 1.0) -> np.ndarray:
+    st = np.zeros((np_, nints), dtype=np.int32)
+    for l in range(np_):
+        L = (l - np_ // 2) * float(p_step)
+        for j in range(nints):
+            u = (j + 0.5) / nints
+            st[l, j] = _opt_reduce(L * (u - 0.5), nbins)
+    return st
+
+
+def orbopt_search(fold: np.ndarray, hits: np.ndarray, m: int, st: np.ndarray) -> Dict:
+    """Step 4 from the definition: dict(best_val, best_idx, centre int32 [nw];
+    tcurve int32 [nw, K]; msum int64 [K])."""
+    fold = np.asarray(fold)
+    K, nints, nbins = fold.shape
+    st = np.asarray(st)
+    np_ = st.shape[0]
+    nw = cube_opt_nwidths(nbins)
+    # d modulo 2^32, read back as int32
+    d = ((fold.astype(np.int64) - int(m) * np.asarray(hits, dtype=np.int64)[None]) & 0xFFFFFFFF).astype(np.uint32) \
+        .view(np.int32).astype(np.int64)
+    b = np.arange(nbins)
+    rot = (b[None, None, :] + st[:, :, None]) % nbins                      # [l, j, b]
+    S = np.zeros((nw, K, np_, nbins), dtype=np.int64)
+    for k in range(K):
+        prof = np.zeros((np_, nbins), dtype=np.int64)
+        for j in range(nints):
+            prof += d[k, j][rot[:, j, :]]
+        box = prof
+        for kw in range(nw):
+            S[kw, k] = box
+            box = box + np.roll(box, -(1 << kw), axis=1)
+    assert np.abs(S).max(initial=0) < 2 ** 31
+    flat = S.reshape(nw, -1)
+    return {"best_val": flat.max(axis=1).astype(np.int32), "best_idx": flat.argmax(axis=1).astype(np.int32),
+            "tcurve": S.max(axis=(2, 3)).astype(np.int32), "centre": S[:, K // 2, np_ // 2].max(axis=1).astype(np.int32),
+            "msum": d.sum(axis=(1, 2)).astype(np.int64)}
+
+
+def orbopt_snr(s: float, w: int, msum: int, v: float, nbins: int) -> float:
+    if not v > 0:
+        return 0.0
+    return (float(s) - w * float(msum) / nbins) / math.sqrt(v * w * (1.0 - float(w) / nbins))
+
+
+def orbopt_finish(cand, grid: Dict, n: int, tsamp: float, m: int, v1: int, hits: np.ndarray, st: np.ndarray,
+                  found: Dict, fold: np.ndarray, p_step: float = 1.0) -> Dict:
+    """Step 5: the record of one candidate.  ``fold`` is [K, nints, nbins]."""
+    P, dm, acc, pb0, a10, ph0 = (float(v) for v in cand)
+    K, nints, nbins = np.asarray(fold).shape
+    np_ = np.asarray(st).shape[0]
+    nw = cube_opt_nwidths(nbins)
+    v = float(v1) / float(nbins)
+    snr = snr_in = 0.0
+    kbest = 0
+    for kw in range(nw):
+        k = int(found["best_idx"][kw]) // nbins // np_
+        s = orbopt_snr(float(int(found["best_val"][kw])), 1 << kw, int(found["msum"][k]), v, nbins)
+        if kw == 0 or s > snr:
+            snr, kbest = s, kw
+        si = orbopt_snr(float(int(found["centre"][kw])), 1 << kw, int(found["msum"][K // 2]), v, nbins)
+        if kw == 0 or si > snr_in:
+            snr_in = si
+    idx = int(found["best_idx"][kbest])
+    ob, ol, ok = idx % nbins, (idx // nbins) % np_, idx // nbins // np_
+    ts = float(np.float32(tsamp))
+    T = float(int(n)) * ts
+    L = (ol - np_ // 2) * float(p_step)
+    kp, ka, kb = ok % grid["nphase"], (ok // grid["nphase"]) % grid["na1"], ok // grid["nphase"] // grid["na1"]
+    face = lambda i, c: c > 1 and i in (0, c - 1)  # noqa: E731
+    flags = 1 if (face(kp, grid["nphase"]) or face(ka, grid["na1"]) or face(kb, grid["npb"]) or face(ol, np_)) else 0
+    if ((abs(float(np.float32(acc))) * T * T) / ((2.0 * C_LIGHT) * P)) * nbins > 1.0:
+        flags |= 2
+    d = ((np.asarray(fold[ok], dtype=np.int64) - int(m) * np.asarray(hits, dtype=np.int64)) & 0xFFFFFFFF) \
+        .astype(np.uint32).view(np.int32).astype(np.int64)
+    bb = np.arange(nbins)
+    prof = np.zeros(nbins, dtype=np.int64)
+    for j in range(nints):
+        prof += d[j, (bb + int(st[ol, j])) % nbins]
+    out = {k2: np.asarray(v2).copy() for k2, v2 in found.items()}
+    t = grid["templates"][ok]
+    out.update(period=P, dm=float(np.float32(dm)), acc=float(np.float32(acc)), pb=pb0, a1=a10, phase=ph0,
+               npb=grid["npb"], na1=grid["na1"], nphase=grid["nphase"], dpb=grid["dpb"], da1=grid["da1"],
+               dph=grid["dph"], snr=snr, snr_in=snr_in, opt_period=1.0 / (1.0 / P - L / (nbins * T)), opt_pb=t[0],
+               opt_a1=t[1], opt_phase=t[2], opt_width=1 << kbest, opt_bin=ob, opt_k=ok, opt_l=ol, flags=flags, m=int(m),
+               v1=int(v1), hits=np.asarray(hits, dtype=np.int32).copy(), fold=np.asarray(fold[ok], dtype=np.int32).copy(),
+               profile=(prof & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
+    return out
+
+
+def orbit_optimise(x: np.ndarray, cand, n: int, tsamp: float, nbins: int = 64, nints: int = 16, npb: int = 9,
+                   na1: int = 9, nphase: int = 9, np_: int = 33, p_step: float = 1.0, pb_step: float = 0.0,
+                   a1_step: float = 0.0, phase_step: float = 0.0, k: int = 0) -> Dict:
+    """The whole chain on one candidate (period, dm, acc, pb, a1, phase) and
+    its dedispersed row ``x``: orbopt_finish's record."""
+    orbopt_check_params(nbins, nints, npb, na1, nphase, np_, p_step, pb_step, a1_step, phase_step)
+    grid = orbopt_grid(cand, n, tsamp, nbins, npb, na1, nphase, pb_step, a1_step, phase_step, k)
+    m, v1 = orbopt_moments(x, n, k)
+    hits = orbopt_hits(n, grid["G"], nints, nbins)
+    fold = orbopt_fold(x, n, grid["G"], grid["quant"], nints, nbins)
+    st = orbopt_drift_table(nints, nbins, np_, p_step)
+    found = orbopt_search(fold, hits, m, st)
+    return orbopt_finish(cand, grid, n, tsamp, m, v1, hits, st, found, fold, p_step)
+
+
+def orbopt_parse_candidates(text: str):
+    """The (period, dm, acc, pb, a1, phase) of a candidate file's text (dm and acc as float32)."""
+    out = []
+    for ln, line in enumerate(text.split("\n"), 1):
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        try:
+            if len(tok) < 6:
+                raise ValueError
+            v = [float(t) for t in tok[:6]]
+        except ValueError:
+            raise ValueError(f"orbopt: candidate line {ln} is malformed") from None
+        out.append((v[0], float(np.float32(v[1])), float(np.float32(v[2])), v[3], v[4], v[5]))
+    return out
